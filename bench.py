@@ -11,7 +11,12 @@ Multi-GPU: one process per GPU (torchrun), each rank synthesises its OWN batch o
 region is bracketed by a barrier + device sync on both sides; the max over ranks is the
 job time; value = all valid mel frames of all ranks / job time.
 
-Also reported:
+A plain run sets up, warms up, times exactly ``--steps`` steps and prints the headline line
+(metric / value / unit / ms_per_step / ...). ``--dump-outputs DIR`` writes what the last timed
+step returned (the forward's ten outputs; in train mode the step's losses) as DIR/<name>.npy;
+inputs and weights are seeded, so two builds run with the same arguments compare output for output.
+
+With ``--full`` the line also carries:
 * roofline — the dominant kernel: the decoder's fused FFN (fs2_ffn: Conv1d k=9 + ReLU + Conv1d
   k=1 + residual + LayerNorm, ~86 % of the FLOPs; the conv-k9 launch pair when the fused kernel
   is off or in fp32 / fp8) timed with HIP events on the stream it launches on; achieved =
@@ -22,6 +27,7 @@ Also reported:
   shape, graph-timed, each with its algorithmic work and roofline fraction (bf16 line).
 * cpu_baseline — the oracle (CPU restatement of the reference, fp32 PyTorch) on a bounded
   sample of the same workload, rank 0 at N=1 only.
+* extra — the other configs (free-running cfg2, cfg4, cfg5 fp8, vocoder, the cfg3 train step).
 """
 import argparse
 import json
@@ -56,11 +62,18 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
                     help="fp8 = cfg5: FFN Conv1d pair of every FFT block on e4m3 MFMA, the rest bf16")
     ap.add_argument("--graph", type=int, default=1, help="replay the forward as a captured HIP graph")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline / per-op tables, the CPU baseline and the "
+                         "extra workloads (--cpu-baseline / --kernel-reps / --vocoder / --extra select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: the oracle's CPU forward rate")
     ap.add_argument("--kernel-reps", type=int, default=20)
-    ap.add_argument("--vocoder", type=int, default=1, help="also time the HiFi-GAN generator on the cfg2 mel batch")
+    ap.add_argument("--vocoder", type=int, default=1,
+                    help="with --full: also time the HiFi-GAN generator on the cfg2 mel batch")
     ap.add_argument("--extra", type=int, default=1,
-                    help="also time free-running cfg2, cfg4 (B=256) and cfg5 (fp8) as extra keys of the JSON line")
+                    help="with --full: also time free-running cfg2, cfg4 (B=256) and cfg5 (fp8) as extra keys of the "
+                         "JSON line")
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "selftest"],
                     help="infer: the headline cfg2 forward; train: the cfg3 train.py step (B=16/GPU, DDP); "
                          "selftest: the launcher / process-group / timing bookkeeping only (gloo, no GPU)")
@@ -494,7 +507,37 @@ def load_traffic(dtype="bf16", fused=False, pre=False):
     return None
 
 
-def train_workload(args, rank, world, device, steps, warmup, ddp=False):
+FORWARD_OUTPUTS = ["mel", "postnet_mel", "p_pred", "e_pred", "log_d", "d_rounded", "src_masks", "mel_masks",
+                   "src_lens", "mel_lens"]
+DUMP_BUDGET_BYTES = 63 * 10 ** 6  # array data; with the .npy headers a dump stays under 64 MB
+
+
+def dump_outputs(dirname, names, tensors, rank=0):
+    """``--dump-outputs``: each tensor as <dirname>/<name>.npy (ranks above 0: <name>.rank<r>.npy),
+    float64 for 64-bit dtypes and float32 for the rest (masks as 0 / 1), whole while they fit
+    DUMP_BUDGET_BYTES together. Otherwise the budget is shared smallest array first (each may take
+    an equal part of what is left), and an array above its part is written as a fixed (seed 0)
+    sample of its flattened elements, in their order."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = []
+    for t in tensors:
+        t = t.detach().cpu()
+        arrays.append(t.to(torch.float64 if t.dtype in (torch.int64, torch.float64) else torch.float32).numpy())
+    left = DUMP_BUDGET_BYTES
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i].nbytes)
+    for k, i in enumerate(order):
+        a = arrays[i]
+        part = left // (len(order) - k)
+        if a.nbytes > part:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, part // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, names[i] + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
+def train_workload(args, rank, world, device, steps, warmup, ddp=False, dump=None):
     """cfg3: one train.py step per iteration (forward, FastSpeech2Loss, backward, RCCL gradient
     all-reduce, clip, ScheduledOptim) on B=16 utterances per GPU, lengths U{16..64}, mel / pitch
     / energy targets N(0,1), timed as the headline is (barrier + device sync on both sides, max over
@@ -530,6 +573,8 @@ def train_workload(args, rank, world, device, steps, warmup, ddp=False):
         parallel.barrier()
         elapsed = time.perf_counter() - t0
         elapsed, tot_frames = parallel.aggregate(elapsed, frames, device)
+        if dump:
+            dump_outputs(dump, ["losses"], [torch.stack([l.detach().float().reshape(()) for l in losses])], rank)
         return {
             "metric": "train mel-frames/sec (cfg3 train.py step, batch 16/GPU, DDP over RCCL)",
             "value": round(tot_frames * steps / elapsed, 1), "unit": "mel-frames/s", "n_gpus": world,
@@ -556,16 +601,19 @@ def main_train(args, rank, world, device):
     """``--mode train``: the cfg3 step (train_workload) as the bench line."""
     from fs2amd import parallel
 
-    rec = train_workload(args, rank, world, device, args.steps, args.warmup, ddp=bool(args.ddp))
+    rec = train_workload(args, rank, world, device, args.steps, args.warmup, ddp=bool(args.ddp),
+                         dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(rec), flush=True)
     parallel.shutdown()
 
 
-def timed_steps(model, batch, device, steps, warmup, graph, frames_out=None):
+def timed_steps(model, batch, device, steps, warmup, graph, frames_out=None, last_out=None):
     """W untimed warmups, then EXACTLY `steps` forwards bracketed by barrier + device sync on both
     sides; returns this rank's elapsed seconds. graph: the forward is captured once as a HIP graph
-    and replayed (needs a sync-free forward: teacher-forced / max_mel_len given)."""
+    and replayed (needs a sync-free forward: teacher-forced / max_mel_len given). last_out: a list
+    that receives the last timed step's outputs (under a graph, its output tensors after the last
+    replay)."""
     from fs2amd import parallel
 
     def step():
@@ -597,10 +645,13 @@ def timed_steps(model, batch, device, steps, warmup, graph, frames_out=None):
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     for _ in range(steps):
-        run()
+        got = run()
     torch.cuda.synchronize(device)
     parallel.barrier()
-    return time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0
+    if last_out is not None:
+        last_out.extend(out if graph or steps < 1 else got)
+    return elapsed
 
 
 def extra_workloads(model, args, rank, device):
@@ -839,6 +890,9 @@ def main():
               file=sys.stderr, flush=True)
     if args.mode == "selftest":
         return main_selftest(args, rank, world, device)
+    # weights and batches are seeded on their own; this fixes what draws from torch's generators
+    # (the train step's dropout seed), so a run's inputs do not depend on what ran before it
+    torch.manual_seed(1 + rank)
     if args.mode == "train":
         return main_train(args, rank, world, device)
 
@@ -853,8 +907,47 @@ def main():
         # static activation scales from a calibration batch of the same shape (different seed)
         model.calibrate_fp8(**to_device(synth_batch(args.batch, args.phonemes, seed=1000 + rank), device))
 
-    elapsed = timed_steps(model, batch, device, args.steps, args.warmup, bool(args.graph))
+    last = []
+    elapsed = timed_steps(model, batch, device, args.steps, args.warmup, bool(args.graph), last_out=last)
     elapsed, tot_frames = parallel.aggregate(elapsed, frames, device)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, FORWARD_OUTPUTS, last, rank)
+    del last
+    ms_per_step = elapsed / args.steps * 1e3
+    value = tot_frames * args.steps / elapsed
+    rec = {
+        "metric": "mel-frames/sec/GPU (batch-64 synth) at 1/2/4/8 MI355X; RTF",
+        "value": round(value, 1),
+        "unit": "mel-frames/s",
+        "per_gpu": round(value / world, 1),  # value is the whole-job aggregate (all ranks' frames / max time)
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (seeded pinyin ids U{64..107}, durations U{2..10} teacher-forced, pitch/energy "
+                "predicted; counter-generated random-init weights)",
+        "config": {"workload": f"cfg2: batch={args.batch} x {args.phonemes} phonemes per GPU, ESD-Chinese-Singing-MFA "
+                               f"model.yaml, FastSpeech2.forward eval {args.dtype}",
+                   "global_batch": args.batch * world, "seq_len": args.phonemes,
+                   "mel_frames_per_gpu_batch": frames, "T_max": int(batch_cpu["max_mel_len"]),
+                   "parallelism": f"dp{world} (independent shards, no collective)",
+                   "hip_graph": bool(args.graph)},
+        "rtf": round((elapsed / args.steps) / (tot_frames / world * HOP / SR), 7),
+    }
+    if args.full:
+        rec.update(full_report(args, model, pc, mc, batch, batch_cpu, frames, rank, world, device))
+    if rank == 0:
+        print(json.dumps(rec), flush=True)
+    parallel.shutdown()
+
+
+def full_report(args, model, pc, mc, batch, batch_cpu, frames, rank, world, device):
+    """``--full``: the keys of the line beyond the headline (module docstring), each from runs of its
+    own after the timed steps."""
     extra = extra_workloads(model, args, rank, device) if args.extra else {}
 
     fwd_t = forward_timers(model, batch)
@@ -878,32 +971,9 @@ def main():
               "HIP events around the last decoder block's fused-FFN launch in 6 eager forwards (blocks 1-5 "
               "also project the next block's Q|K|V: 'with_next_qkv')" if fused else
               "HIP events around each decoder conv-k9 op call (both launches) in 6 eager forwards")
-    ms_per_step = elapsed / args.steps * 1e3
-    value = tot_frames * args.steps / elapsed
     peak = {"bf16": BF16_PEAK_TFLOPS, "fp8": FP8_PEAK_TFLOPS}.get(args.dtype, F32_PEAK_TFLOPS)
     achieved = kernel_flops / kernel_s / 1e12
     rec = {
-        "metric": "mel-frames/sec/GPU (batch-64 synth) at 1/2/4/8 MI355X; RTF",
-        "value": round(value, 1),
-        "unit": "mel-frames/s",
-        "per_gpu": round(value / world, 1),  # value is the whole-job aggregate (all ranks' frames / max time)
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic (seeded pinyin ids U{64..107}, durations U{2..10} teacher-forced, pitch/energy "
-                "predicted; counter-generated random-init weights)",
-        "config": {"workload": f"cfg2: batch={args.batch} x {args.phonemes} phonemes per GPU, ESD-Chinese-Singing-MFA "
-                               f"model.yaml, FastSpeech2.forward eval {args.dtype}",
-                   "global_batch": args.batch * world, "seq_len": args.phonemes,
-                   "mel_frames_per_gpu_batch": frames, "T_max": int(batch_cpu["max_mel_len"]),
-                   "parallelism": f"dp{world} (independent shards, no collective)",
-                   "hip_graph": bool(args.graph)},
-        "rtf": round((elapsed / args.steps) / (tot_frames / world * HOP / SR), 7),
         "roofline": {"bound": "mfma", "kernel": ("decoder FFT block after attention (bf16): ffn_fused_kernel<PRE> = fc "
                                                  "256->256 + residual + LayerNorm, Conv1d k=9 256->1024 + ReLU + "
                                                  "Conv1d k=1 1024->256 + residual + LayerNorm, one launch"
@@ -948,9 +1018,7 @@ def main():
         rec["cpu_baseline"] = cpu_baseline(batch_cpu, pc, mc)
     if extra:
         rec["extra"] = extra
-    if rank == 0:
-        print(json.dumps(rec), flush=True)
-    parallel.shutdown()
+    return rec
 
 
 if __name__ == "__main__":

@@ -10,6 +10,8 @@ import torch
 from fs2amd import config as C
 from fs2amd.synth_weights import synth_state_dict
 
+from _npz_parts import load_npz_parts
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
 
@@ -44,7 +46,7 @@ def oracle_state_dict():
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    z = load_npz_parts(os.path.join(GOLDEN, name + ".npz"))
     args, outs = {}, {}
     for k in z.files:
         if k.startswith("in_"):
@@ -60,7 +62,7 @@ def load_train_case(name="train_grads"):
     """tests/golden/<name>.npz (train_grads: B=4, train_b16: the cfg3 shape B=16, lengths
     U{16..64}): inputs, reference losses, per-parameter gradient sums / sums of squares / 16
     sampled elements, BN running stats after the step."""
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    z = load_npz_parts(os.path.join(GOLDEN, name + ".npz"))
     args = {}
     for k in z.files:
         if k.startswith("in_"):

@@ -29,10 +29,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = os.environ.get("FS2_REFERENCE", "/root/reference")
 sys.path.insert(0, os.path.join(REPO, "expressive-fastspeech2-mandarin_amd"))
+sys.path.insert(0, os.path.dirname(HERE))
 
 from fs2amd import config as C  # noqa: E402
 from fs2amd.data import synth_batch  # noqa: E402
 from fs2amd.synth_weights import fill_module  # noqa: E402
+
+from _npz_parts import save_npz_parts  # noqa: E402  (no file under tests/golden/ above 1 MiB)
 
 
 def _stub(name):
@@ -112,7 +115,7 @@ def run_case(model, LR, name, args, controls=(1.0, 1.0, 1.0), save_full=True, he
     for a, b in frames:  # frame slices of every utterance
         rec[f"out_postnet_mel_f{a}_{b}"] = t2n(outs[1][:, a:b])
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **rec)
+    save_npz_parts(path, **rec)
     print(f"{name}: {os.path.getsize(path) / 1e3:.1f} kB  mel {tuple(outs[0].shape)}")
 
 
@@ -182,7 +185,7 @@ def train_case(FastSpeech2, pc, mc, sd, name="train_grads", shape=(4, 10, 24), s
             rec["bn_" + bname] = t2n(buf)
     rec["out_mel_lens"] = t2n(out[9])
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **rec)
+    save_npz_parts(path, **rec)
     print(f"{name}: {os.path.getsize(path) / 1e3:.1f} kB, {len(keys)} grads, losses {rec['losses']}")
 
 
@@ -388,7 +391,7 @@ def pipeline_case(pc, mc):
         rec[f"text__{k}"] = v.numpy() if torch.is_tensor(v) else np.array(v)
         if torch.is_tensor(v):
             rec[f"text__{k}__dtype"] = np.array(str(v.dtype))
-    np.savez_compressed(os.path.join(HERE, "pipeline_batches.npz"), **rec)
+    save_npz_parts(os.path.join(HERE, "pipeline_batches.npz"), **rec)
     print("pipeline_batches:", {k: int(v) for k, v in rec.items() if k.endswith("__n")})
 
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from _common import GOLDEN, configs, oracle_state_dict
+from _npz_parts import load_npz_parts
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,7 +33,7 @@ def _cfg(corpus):
 def test_packed_h2d_matches_reference_to_device(corpus):
     from fs2amd.pipeline import Dataset, to_device
 
-    ref = np.load(os.path.join(GOLDEN, "pipeline_batches.npz"))
+    ref = load_npz_parts(os.path.join(GOLDEN, "pipeline_batches.npz"))
     pc, mc, tc = _cfg(corpus)
     ds = Dataset("train.txt", pc, mc, tc, sort=True)
     batches = ds.collate_fn([ds[i] for i in range(len(ds))])

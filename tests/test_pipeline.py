@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from _common import GOLDEN, configs
+from _npz_parts import load_npz_parts
 
 
 @pytest.fixture(scope="module")
@@ -23,7 +24,7 @@ def corpus(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def ref():
-    return np.load(os.path.join(GOLDEN, "pipeline_batches.npz"))
+    return load_npz_parts(os.path.join(GOLDEN, "pipeline_batches.npz"))
 
 
 def _cfg(corpus):

@@ -8,7 +8,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o bench --output-format csv -- \
-  python3 bench.py --steps 10 --warmup 3 --cpu-baseline 0 > $OUT/bench_under_rocprof.log 2>&1 || exit $?
+  python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline 0 > $OUT/bench_under_rocprof.log 2>&1 || exit $?
 for K in ${PROBE_KERNELS:-conv9 lr}; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $C -T -d $OUT/pmc_${K}_$C -o pmc --output-format csv -- \

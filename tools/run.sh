@@ -6,8 +6,8 @@
 #   tests[=PYTEST_TARGETS]  pytest -m gpu (default: the whole tests/ dir; comma-separated targets, e.g.
 #                           tests=tests/test_gpu_ops.py,tests/test_gpu_ffn.py)
 #   smoke                   __graft_entry__.smoke()
-#   bench                   the default bench line (50 / 20, all extra keys)
-#   driver                  the driver's protocol: --gpus 1 --steps 20 --warmup 5
+#   bench                   bench.py --full: the default 50 / 20 line with the roofline tables and all extra keys
+#   driver                  a plain headline run: --gpus 1 --steps 20 --warmup 5
 #   train                   bench.py --mode train --graph 1 (cfg3 line)
 #   free / free_eager       tools/free_probe.py (SynthGraphs / eager), 8 distinct batches
 #   fwd_trace               rocprofv3 kernel trace of the bench -> forward_kernels.txt
@@ -32,7 +32,7 @@ for st in "$@"; do
       timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || fail $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $O/bench.log 2>&1 || fail $O/bench.log
+      timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1 || fail $O/bench.log
       tail -1 $O/bench.log | cut -c1-300 ;;
     driver)
       timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || fail $O/bench_driver.log
