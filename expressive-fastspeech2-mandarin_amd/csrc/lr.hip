@@ -16,14 +16,16 @@
 #include <type_traits>
 
 #include "fs2_common.h"
+#include "fs2hip_prosody.h"
 
 namespace {
 
 constexpr int kScanThreads = 256;
 constexpr int kLdsCum = 2048;  // cum rows up to this many phonemes are searched in LDS
 
-__device__ __forceinline__ int64_t frames_of(const void *dur, int kind, float d_control, int64_t idx,
-                                             float *d_rounded) {
+// d_map (optional, FS2_DUR_LOGPRED only): a per-phoneme duration control, indexed like dur
+__device__ __forceinline__ int64_t frames_of(const void *dur, int kind, float d_control, const float *d_map,
+                                             int64_t idx, float *d_rounded) {
   if (kind == FS2_DUR_I64) {
     int64_t d = reinterpret_cast<const int64_t *>(dur)[idx];
     return d > 0 ? d : 0;
@@ -31,7 +33,7 @@ __device__ __forceinline__ int64_t frames_of(const void *dur, int kind, float d_
   float v = reinterpret_cast<const float *>(dur)[idx];
   if (kind == FS2_DUR_LOGPRED) {
     // torch.clamp(torch.round(torch.exp(log_d) - 1) * d_control, min=0)  (modules.py:132-135)
-    float r = rintf(expf(v) - 1.0f) * d_control;
+    float r = rintf(expf(v) - 1.0f) * (d_map != nullptr ? d_map[idx] : d_control);
     r = r < 0.0f ? 0.0f : r;
     if (d_rounded) d_rounded[idx] = r;
     v = r;
@@ -42,8 +44,9 @@ __device__ __forceinline__ int64_t frames_of(const void *dur, int kind, float d_
   return (int64_t)v;
 }
 
-__global__ __launch_bounds__(kScanThreads) void lr_durations_kernel(const void *dur, int kind, float d_control, int L,
-                                                                    int32_t *cum, int64_t *mel_len, float *d_rounded) {
+__global__ __launch_bounds__(kScanThreads) void lr_durations_kernel(const void *dur, int kind, float d_control,
+                                                                    const float *d_map, int L, int32_t *cum,
+                                                                    int64_t *mel_len, float *d_rounded) {
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(kScanThreads) void lr_durations_kernel(const void *
   const int64_t base = (int64_t)b * L;
 
   int64_t local = 0;
-  for (int i = i0; i < i1; ++i) local += frames_of(dur, kind, d_control, base + i, nullptr);
+  for (int i = i0; i < i1; ++i) local += frames_of(dur, kind, d_control, d_map, base + i, nullptr);
 
   // inclusive wave scan, then across the 4 waves through LDS
   int64_t incl = local;
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(kScanThreads) void lr_durations_kernel(const void *
   int64_t run = prefix + incl - local;  // exclusive prefix of this thread's span
 
   for (int i = i0; i < i1; ++i) {
-    run += frames_of(dur, kind, d_control, base + i, d_rounded);
+    run += frames_of(dur, kind, d_control, d_map, base + i, d_rounded);
     cum[base + i] = (int32_t)(run < 0x7fffffff ? run : 0x7fffffff);
   }
   if (tid == kScanThreads - 1) {
@@ -235,6 +238,7 @@ struct LrFusedArgs {
   const void *dur;
   int dur_kind;
   float d_control;
+  const float *d_map;  // optional per-phoneme duration control [B, L] (FS2_DUR_LOGPRED)
   const int32_t *cum_in;
   const int64_t *mel_len_in;
   const int64_t *lens;  // layout lengths (the decoder's mel lengths)
@@ -287,7 +291,7 @@ __global__ __launch_bounds__(256) void lr_fused_kernel(LrFusedArgs a) {
     const int i0 = min(tid * per, L), i1 = min(i0 + per, L);
     const int64_t base = (int64_t)b * L;
     int64_t local = 0;
-    for (int i = i0; i < i1; ++i) local += frames_of(a.dur, a.dur_kind, a.d_control, base + i, nullptr);
+    for (int i = i0; i < i1; ++i) local += frames_of(a.dur, a.dur_kind, a.d_control, a.d_map, base + i, nullptr);
     int64_t incl = local;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -299,7 +303,7 @@ __global__ __launch_bounds__(256) void lr_fused_kernel(LrFusedArgs a) {
     int64_t run = incl - local;
     for (int w = 0; w < wv; ++w) run += wtot[w];
     for (int i = i0; i < i1; ++i) {
-      run += frames_of(a.dur, a.dur_kind, a.d_control, base + i, first ? a.d_rounded : nullptr);
+      run += frames_of(a.dur, a.dur_kind, a.d_control, a.d_map, base + i, first ? a.d_rounded : nullptr);
       const int32_t c = (int32_t)(run < 0x7fffffff ? run : 0x7fffffff);
       scum[i] = c;
       if (first) a.cum[base + i] = c;
@@ -625,15 +629,21 @@ extern "C" int fs2_length_masks(const int64_t *lens, int B, int width, bool *mas
   return FS2_OK;
 }
 
-extern "C" int fs2_lr_durations(const void *dur, int dur_kind, float d_control, int B, int L, int32_t *cum,
-                                int64_t *mel_len, float *d_rounded, fs2_stream_t stream) {
+extern "C" int fs2_lr_durations_map(const void *dur, int dur_kind, float d_control, const float *d_map, int B, int L,
+                                    int32_t *cum, int64_t *mel_len, float *d_rounded, fs2_stream_t stream) {
   if (dur == nullptr || cum == nullptr || mel_len == nullptr || B < 0 || L <= 0) return FS2_EINVAL;
   if (dur_kind < FS2_DUR_I64 || dur_kind > FS2_DUR_LOGPRED) return FS2_EINVAL;
+  if (d_map != nullptr && dur_kind != FS2_DUR_LOGPRED) return FS2_EINVAL;  // a map scales predictions only
   if (B == 0) return FS2_OK;
   hipLaunchKernelGGL(lr_durations_kernel, dim3(B), dim3(kScanThreads), 0, as_stream(stream), dur, dur_kind, d_control,
-                     L, cum, mel_len, d_rounded);
+                     d_map, L, cum, mel_len, d_rounded);
   FS2_CHECK_LAUNCH();
   return FS2_OK;
+}
+
+extern "C" int fs2_lr_durations(const void *dur, int dur_kind, float d_control, int B, int L, int32_t *cum,
+                                int64_t *mel_len, float *d_rounded, fs2_stream_t stream) {
+  return fs2_lr_durations_map(dur, dur_kind, d_control, nullptr, B, L, cum, mel_len, d_rounded, stream);
 }
 
 extern "C" int fs2_lr_expand(const void *x, int x_dtype, const int32_t *cum, const int64_t *mel_len, int B, int L,
@@ -689,7 +699,9 @@ __global__ __launch_bounds__(256) void lr_pad_kernel(LrFusedArgs a) {
   int64_t local = 0;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
-    fr[k] = i0 + k < i1 ? frames_of(a.dur, a.dur_kind, a.d_control, base + i0 + k, first ? a.d_rounded : nullptr) : 0;
+    fr[k] = i0 + k < i1 ? frames_of(a.dur, a.dur_kind, a.d_control, a.d_map, base + i0 + k,
+                                    first ? a.d_rounded : nullptr)
+                        : 0;
     local += fr[k];
   }
   int64_t incl = local;
@@ -784,14 +796,23 @@ static void lr_pad_launch(const LrFusedArgs &a, int fr, hipStream_t s) {
 extern "C" int fs2_length_regulate(const void *x, int x_dtype, const void *dur, int dur_kind, float d_control, int B,
                                    int L, int D, int T_out, const float *pe, void *out, int out_dtype, int32_t *cum,
                                    int64_t *mel_len, float *d_rounded, int32_t *index_map, fs2_stream_t stream) {
+  return fs2_length_regulate_map(x, x_dtype, dur, dur_kind, d_control, nullptr, B, L, D, T_out, pe, out, out_dtype, cum,
+                                 mel_len, d_rounded, index_map, stream);
+}
+
+extern "C" int fs2_length_regulate_map(const void *x, int x_dtype, const void *dur, int dur_kind, float d_control,
+                                       const float *d_map, int B, int L, int D, int T_out, const float *pe, void *out,
+                                       int out_dtype, int32_t *cum, int64_t *mel_len, float *d_rounded,
+                                       int32_t *index_map, fs2_stream_t stream) {
   if (x == nullptr || dur == nullptr || cum == nullptr || mel_len == nullptr) return FS2_EINVAL;
   if (dur_kind < FS2_DUR_I64 || dur_kind > FS2_DUR_LOGPRED) return FS2_EINVAL;
+  if (d_map != nullptr && dur_kind != FS2_DUR_LOGPRED) return FS2_EINVAL;  // a map scales predictions only
   if (dur_kind == FS2_DUR_LOGPRED && d_rounded == nullptr) return FS2_EINVAL;
   if (out == nullptr && index_map == nullptr) return FS2_EINVAL;
   if (B < 0 || L <= 0 || D <= 0 || (D & 7) != 0 || T_out < 0 || (int64_t)B * T_out > 0x7fffff00LL) return FS2_EINVAL;
   if (B == 0) return FS2_OK;
   if (T_out == 0 || L > kLdsCum || out == nullptr) {  // long phoneme rows / map only: the two-launch form
-    const int rc = fs2_lr_durations(dur, dur_kind, d_control, B, L, cum, mel_len, d_rounded, stream);
+    const int rc = fs2_lr_durations_map(dur, dur_kind, d_control, d_map, B, L, cum, mel_len, d_rounded, stream);
     if (rc != FS2_OK || T_out == 0) return rc;
     return fs2_lr_expand(x, x_dtype, cum, mel_len, B, L, D, T_out, pe, out, out_dtype, index_map, nullptr, stream);
   }
@@ -800,6 +821,7 @@ extern "C" int fs2_length_regulate(const void *x, int x_dtype, const void *dur, 
   a.dur = dur;
   a.dur_kind = dur_kind;
   a.d_control = d_control;
+  a.d_map = d_map;
   a.B = B;
   a.L = L;
   a.D = D;
@@ -869,6 +891,19 @@ extern "C" int fs2_lr_fused_proj(const void *x, int x_dtype, const void *dur, in
                                  int32_t *rowmap, void *out, int out_dtype, int32_t *cum, int64_t *mel_len,
                                  float *d_rounded, const float *proj_src, const float *proj_pe, int NP,
                                  void *proj_out, fs2_stream_t stream) {
+  return fs2_lr_fused_proj_map(x, x_dtype, dur, dur_kind, d_control, nullptr, cum_in, mel_len_in, B, L, D, T_out, pe,
+                               layout_lens, cu, row_pos, rowmap, out, out_dtype, cum, mel_len, d_rounded, proj_src,
+                               proj_pe, NP, proj_out, stream);
+}
+
+extern "C" int fs2_lr_fused_proj_map(const void *x, int x_dtype, const void *dur, int dur_kind, float d_control,
+                                     const float *d_map, const int32_t *cum_in, const int64_t *mel_len_in, int B,
+                                     int L, int D, int T_out, const float *pe, const int64_t *layout_lens, int32_t *cu,
+                                     int32_t *row_pos, int32_t *rowmap, void *out, int out_dtype, int32_t *cum,
+                                     int64_t *mel_len, float *d_rounded, const float *proj_src, const float *proj_pe,
+                                     int NP, void *proj_out, fs2_stream_t stream) {
+  // a map scales predictions only: it needs the scan mode and log-duration input
+  if (d_map != nullptr && (dur == nullptr || dur_kind != FS2_DUR_LOGPRED)) return FS2_EINVAL;
   if (proj_out != nullptr && (proj_src == nullptr || proj_pe == nullptr || NP < 8 || NP > 1536 || (NP & 7) != 0))
     return FS2_EINVAL;
   if (x == nullptr || out == nullptr || layout_lens == nullptr || cu == nullptr) return FS2_EINVAL;
@@ -884,7 +919,7 @@ extern "C" int fs2_lr_fused_proj(const void *x, int x_dtype, const void *dur, in
   if (T_out == 0) {
     // nothing to gather, but the scan outputs and cu are still due: one frame block of work
     if (dur != nullptr) {
-      int rc = fs2_lr_durations(dur, dur_kind, d_control, B, L, cum, mel_len, d_rounded, stream);
+      int rc = fs2_lr_durations_map(dur, dur_kind, d_control, d_map, B, L, cum, mel_len, d_rounded, stream);
       if (rc != FS2_OK) return rc;
     }
     return fs2_seq_layout(layout_lens, B, 0, cu, row_pos, rowmap, stream);
@@ -894,6 +929,7 @@ extern "C" int fs2_lr_fused_proj(const void *x, int x_dtype, const void *dur, in
   a.dur = dur;
   a.dur_kind = dur_kind;
   a.d_control = d_control;
+  a.d_map = d_map;
   a.cum_in = cum_in;
   a.mel_len_in = mel_len_in;
   a.lens = layout_lens;

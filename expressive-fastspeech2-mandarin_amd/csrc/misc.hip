@@ -2,6 +2,7 @@
 // per-utterance speaker/emotion conditioning vectors, and the pitch/energy bucketize +
 // embedding add of the VarianceAdaptor.
 #include "fs2_common.h"
+#include "fs2hip_prosody.h"
 #include "cond.h"
 
 namespace {
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(256) void cond_kernel(CondArgs a) {
 template <typename TX>
 __global__ __launch_bounds__(256) void variance_embed_kernel(const TX *x, TX *out, const float *pred, float *pred_out,
                                                              const float *__restrict__ target, float control,
+                                                             const float *__restrict__ control_map,
                                                              const float *__restrict__ bins, int nb,
                                                              const float *__restrict__ table, int M, int D,
                                                              int64_t *__restrict__ idx_out) {
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void variance_embed_kernel(const TX *x, TX *ou
   if (target != nullptr) {
     v = target[m];
   } else {
-    v = pred[m] * control;
+    v = pred[m] * (control_map != nullptr ? control_map[m] : control);  // the row's own factor with a map
   }
   // torch.bucketize(v, bins, right=False): number of boundaries strictly below v
   int lo = 0, hi = nb;
@@ -172,8 +174,9 @@ extern "C" int fs2_cond_vectors(const int64_t *speakers, const float *speaker_ta
 }
 
 static int variance_embed_launch(const void *x, int x_dtype, void *out, const float *pred, float *pred_out,
-                                 const float *target, float control, const float *bins, int n_bins,
-                                 const float *table, int M, int D, int64_t *idx_out, fs2_stream_t stream) {
+                                 const float *target, float control, const float *control_map, const float *bins,
+                                 int n_bins, const float *table, int M, int D, int64_t *idx_out,
+                                 fs2_stream_t stream) {
   if (x == nullptr || out == nullptr || (pred == nullptr && target == nullptr) || bins == nullptr || table == nullptr)
     return FS2_EINVAL;
   if (M < 0 || D <= 0 || (D & 7) || n_bins < 2) return FS2_EINVAL;
@@ -182,12 +185,12 @@ static int variance_embed_launch(const void *x, int x_dtype, void *out, const fl
   hipStream_t s = as_stream(stream);
   if (x_dtype == FS2_F32)
     hipLaunchKernelGGL(variance_embed_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(x),
-                       reinterpret_cast<float *>(out), pred, pred_out, target, control, bins, n_bins - 1, table, M, D,
-                       idx_out);
+                       reinterpret_cast<float *>(out), pred, pred_out, target, control, control_map, bins, n_bins - 1,
+                       table, M, D, idx_out);
   else if (x_dtype == FS2_BF16)
     hipLaunchKernelGGL(variance_embed_kernel<bf16>, grid, dim3(256), 0, s, reinterpret_cast<const bf16 *>(x),
-                       reinterpret_cast<bf16 *>(out), pred, pred_out, target, control, bins, n_bins - 1, table, M, D,
-                       idx_out);
+                       reinterpret_cast<bf16 *>(out), pred, pred_out, target, control, control_map, bins, n_bins - 1,
+                       table, M, D, idx_out);
   else
     return FS2_EUNSUPPORTED;
   FS2_CHECK_LAUNCH();
@@ -197,16 +200,23 @@ static int variance_embed_launch(const void *x, int x_dtype, void *out, const fl
 extern "C" int fs2_variance_embed(void *x, int x_dtype, float *pred, const float *target, float control,
                                   const float *bins, int n_bins, const float *table, int M, int D,
                                   fs2_stream_t stream) {
+  return fs2_variance_embed_map(x, x_dtype, pred, target, control, nullptr, bins, n_bins, table, M, D, stream);
+}
+
+extern "C" int fs2_variance_embed_map(void *x, int x_dtype, float *pred, const float *target, float control,
+                                      const float *control_map, const float *bins, int n_bins, const float *table,
+                                      int M, int D, fs2_stream_t stream) {
   if (pred == nullptr) return FS2_EINVAL;
-  return variance_embed_launch(x, x_dtype, x, pred, pred, target, control, bins, n_bins, table, M, D, nullptr, stream);
+  return variance_embed_launch(x, x_dtype, x, pred, pred, target, control, control_map, bins, n_bins, table, M, D,
+                               nullptr, stream);
 }
 
 extern "C" int fs2_variance_embed_ex(const void *x, int x_dtype, const float *value, const float *bins, int n_bins,
                                      const float *table, int M, int D, void *out, int64_t *idx_out,
                                      fs2_stream_t stream) {
   if (value == nullptr) return FS2_EINVAL;
-  return variance_embed_launch(x, x_dtype, out, nullptr, nullptr, value, 1.0f, bins, n_bins, table, M, D, idx_out,
-                               stream);
+  return variance_embed_launch(x, x_dtype, out, nullptr, nullptr, value, 1.0f, nullptr, bins, n_bins, table, M, D,
+                               idx_out, stream);
 }
 
 extern "C" const char *fs2_version(void) { return "fs2hip 0.1.0 (gfx950)"; }

@@ -20,6 +20,7 @@
 
 #include "conv_common.h"
 #include "fs2_common.h"
+#include "fs2hip_prosody.h"
 
 namespace {
 
@@ -84,6 +85,7 @@ __global__ __launch_bounds__(256) void vp_head_kernel(const float *__restrict__ 
                                                       const int64_t *__restrict__ lens, float *__restrict__ pred,
                                                       int embed_g, TX *__restrict__ x, int64_t xs, int D,
                                                       const float *__restrict__ target, float control,
+                                                      const float *__restrict__ control_map,
                                                       const float *__restrict__ bins, int nb,
                                                       const float *__restrict__ table) {
   const int64_t item = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
@@ -106,8 +108,9 @@ __global__ __launch_bounds__(256) void vp_head_kernel(const float *__restrict__ 
     return;
   }
   // pitch / energy embedding (fs2_variance_embed semantics): target given -> bucketize the target
-  // and keep the prediction; otherwise the prediction is scaled by control first
-  const float val = target != nullptr ? target[m] : p * control;
+  // and keep the prediction; otherwise the prediction is scaled by control (the row's own factor
+  // when a control map is given) first
+  const float val = target != nullptr ? target[m] : p * (control_map != nullptr ? control_map[m] : control);
   if (sub == 0) pred[(int64_t)g * M + m] = target != nullptr ? p : val;
   int lo = 0, hi = nb;  // torch.bucketize(val, bins, right=False)
   while (lo < hi) {
@@ -177,6 +180,7 @@ struct VpArgs {
   int64_t xos;
   const float *target;
   float control;
+  const float *control_map;  // optional per-row control [M], indexed like target
   const float *bins;
   int nb;             // number of bin edges (n_bins - 1)
   const float *table; // [n_bins][256]
@@ -582,8 +586,9 @@ __global__ __launch_bounds__(256, 1) void vp_fused_kernel(VpArgs p) {
           p.pred[(size_t)g * M + gm] = pv;
         } else {
           // fs2_variance_embed semantics: a target is bucketized as given (the prediction kept);
-          // otherwise the prediction is scaled by control first
-          const float val = p.target != nullptr ? p.target[gm] : pv * p.control;
+          // otherwise the prediction is scaled by control (the row's own factor with a map) first
+          const float val =
+              p.target != nullptr ? p.target[gm] : pv * (p.control_map != nullptr ? p.control_map[gm] : p.control);
           p.pred[(size_t)g * M + gm] = p.target != nullptr ? pv : val;
           int lo = 0, hb = p.nb;  // torch.bucketize(val, bins, right=False)
           while (lo < hb) {
@@ -618,7 +623,7 @@ __global__ __launch_bounds__(256, 1) void vp_fused_kernel(VpArgs p) {
 
 extern "C" int64_t fs2_vp_fused_weight_elems(int G) { return (int64_t)G * 4 * kVpWaveBytes / 2; }
 
-extern "C" int fs2_vp_fused(const fs2_vp_fused_desc *d, fs2_stream_t stream) {
+static int vp_fused_launch(const fs2_vp_fused_desc *d, const float *control_map, fs2_stream_t stream) {
   if (d == nullptr || d->x == nullptr || d->w == nullptr || d->vec == nullptr || d->lin_b == nullptr ||
       d->lens == nullptr || d->pred == nullptr)
     return FS2_EINVAL;
@@ -652,6 +657,7 @@ extern "C" int fs2_vp_fused(const fs2_vp_fused_desc *d, fs2_stream_t stream) {
   p.xos = d->x_out_row_stride;
   p.target = d->target;
   p.control = d->control;
+  p.control_map = d->embed_group >= 0 ? control_map : nullptr;
   p.bins = d->bins;
   p.nb = d->n_bins - 1;
   p.table = d->table;
@@ -664,6 +670,15 @@ extern "C" int fs2_vp_fused(const fs2_vp_fused_desc *d, fs2_stream_t stream) {
   hipLaunchKernelGGL(vp_fused_kernel, dim3(nwg), dim3(256), 0, as_stream(stream), p);
   FS2_CHECK_LAUNCH();
   return FS2_OK;
+}
+
+extern "C" int fs2_vp_fused(const fs2_vp_fused_desc *d, fs2_stream_t stream) {
+  return vp_fused_launch(d, nullptr, stream);
+}
+
+extern "C" int fs2_vp_fused_map(const fs2_vp_fused_map_desc *d, fs2_stream_t stream) {
+  if (d == nullptr) return FS2_EINVAL;
+  return vp_fused_launch(&d->base, d->control_map, stream);
 }
 
 extern "C" int fs2_vp_norm(const float *y, int64_t y_row_stride, int M, int G, int C, const float *gamma,
@@ -686,6 +701,16 @@ extern "C" int fs2_vp_head(const float *y, int64_t y_row_stride, int B, int T, i
                            float *pred, int embed_group, void *x, int x_dtype, int64_t x_row_stride, int D,
                            const float *target, float control, const float *bins, int n_bins, const float *table,
                            fs2_stream_t stream) {
+  return fs2_vp_head_map(y, y_row_stride, B, T, G, C, gamma, beta, eps, lin_w, lin_b, lens, pred, embed_group, x,
+                         x_dtype, x_row_stride, D, target, control, nullptr, bins, n_bins, table, stream);
+}
+
+extern "C" int fs2_vp_head_map(const float *y, int64_t y_row_stride, int B, int T, int G, int C, const float *gamma,
+                               const float *beta, float eps, const float *lin_w, const float *lin_b,
+                               const int64_t *lens, float *pred, int embed_group, void *x, int x_dtype,
+                               int64_t x_row_stride, int D, const float *target, float control,
+                               const float *control_map, const float *bins, int n_bins, const float *table,
+                               fs2_stream_t stream) {
   if (y == nullptr || gamma == nullptr || beta == nullptr || lin_w == nullptr || lin_b == nullptr ||
       lens == nullptr || pred == nullptr)
     return FS2_EINVAL;
@@ -707,11 +732,11 @@ extern "C" int fs2_vp_head(const float *y, int64_t y_row_stride, int B, int T, i
   if (embed_group >= 0 && x_dtype == FS2_F32)
     hipLaunchKernelGGL(vp_head_kernel<float>, grid, dim3(256), 0, s, y, y_row_stride, T, M, G, gamma, beta, eps, lin_w,
                        lin_b, lens, pred, embed_group, reinterpret_cast<float *>(x), x_row_stride, D, target, control,
-                       bins, n_bins - 1, table);
+                       control_map, bins, n_bins - 1, table);
   else
     hipLaunchKernelGGL(vp_head_kernel<bf16>, grid, dim3(256), 0, s, y, y_row_stride, T, M, G, gamma, beta, eps, lin_w,
                        lin_b, lens, pred, embed_group, reinterpret_cast<bf16 *>(x), x_row_stride, D, target, control,
-                       bins, n_bins - 1, table);
+                       control_map, bins, n_bins - 1, table);
   FS2_CHECK_LAUNCH();
   return FS2_OK;
 }

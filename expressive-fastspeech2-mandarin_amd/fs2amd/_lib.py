@@ -160,6 +160,12 @@ class VpFusedDesc(ctypes.Structure):
     ]
 
 
+class VpFusedMapDesc(ctypes.Structure):
+    """Mirror of ``fs2_vp_fused_map_desc`` (include/fs2hip_prosody.h)."""
+
+    _fields_ = [("base", VpFusedDesc), ("control_map", _p)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "fs2_version": (ctypes.c_char_p, []),
@@ -243,6 +249,20 @@ SIGNATURES = {
 }
 
 
+# include/fs2hip_prosody.h: the control-map siblings (the scalar entry's arguments plus the map
+# pointer after the scalar control; NULL = the scalar)
+SIGNATURES_PROSODY = {
+    "fs2_lr_durations_map": (_i, [_p, _i, _f, _p, _i, _i, _p, _p, _p, _p]),
+    "fs2_length_regulate_map": (_i, [_p, _i, _p, _i, _f, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "fs2_lr_fused_proj_map": (_i, [_p, _i, _p, _i, _f, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p,
+                                   _p, _p, _p, _i, _p, _p]),
+    "fs2_variance_embed_map": (_i, [_p, _i, _p, _p, _f, _p, _p, _i, _p, _i, _i, _p]),
+    "fs2_vp_head_map": (_i, [_p, _i64, _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p, _i, _p, _i, _i64, _i, _p, _f, _p, _p,
+                             _i, _p, _p]),
+    "fs2_vp_fused_map": (_i, [ctypes.POINTER(VpFusedMapDesc), _p]),
+}
+
+
 def header_symbols(header_path):
     """Every ``fs2_*`` function declared in include/fs2hip.h (for the export test)."""
     import re
@@ -254,11 +274,15 @@ def header_symbols(header_path):
 _LIB = None
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "fs2hip.h")
+HEADER_PROSODY = os.path.join(os.path.dirname(HEADER), "fs2hip_prosody.h")
+# public headers beside fs2hip.h that the sources include: part of the build id
+EXTRA_HEADERS = ("fs2hip_prosody.h",)
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
-    """sha256 (first 16 hex digits) of csrc/*.hip, csrc/*.h and include/fs2hip.h, in name order:
-    the id __graft_entry__.build_hip embeds as fs2_build_id(). None when the sources are absent."""
+    """sha256 (first 16 hex digits) of csrc/*.hip, csrc/*.h, include/fs2hip.h and the EXTRA_HEADERS
+    beside it, in name order: the id __graft_entry__.build_hip embeds as fs2_build_id(). None when
+    the sources are absent."""
     import hashlib
 
     if not os.path.isdir(csrc) or not os.path.exists(header):
@@ -271,6 +295,10 @@ def source_build_id(csrc=CSRC, header=HEADER):
     with open(header, "rb") as f:
         h.update(b"fs2hip.h")
         h.update(f.read())
+    for name in EXTRA_HEADERS:
+        with open(os.path.join(os.path.dirname(header), name), "rb") as f:
+            h.update(name.encode())
+            h.update(f.read())
     return h.hexdigest()[:16]
 
 
@@ -292,7 +320,7 @@ def load():
     # FS2_LIB_ALLOW_MISSING=1 (A/B runs against an older library build only): skip entry points
     # the override library does not export; calling one of them then raises AttributeError.
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

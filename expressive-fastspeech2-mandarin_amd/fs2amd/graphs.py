@@ -5,8 +5,8 @@ durations: the decoder length T_out = max(mel_len) is known only after the durat
 has run, so the path has one device->host read (runtime.host_meta) and cannot be ONE graph.
 :class:`SynthGraphs` captures the two halves:
 
-* stage 1 (keyed by B, L_max and the control values; an LRU of ``max_stage1`` graphs): token
-  embedding + PE, the encoder, the
+* stage 1 (keyed by B, L_max and the controls -- a number by its value, a control map by a marker;
+  an LRU of ``max_stage1`` graphs): token embedding + PE, the encoder, the
   variance adaptor and the LengthRegulator scan (duration rounding, cumulative frames, mel_len),
   plus the int32 meta vector [max(mel_len), sum(mel_len), out-of-vocabulary count];
 * the host reads the meta vector (one sync), raises IndexError on bad ids;
@@ -77,6 +77,18 @@ def _spin_until_landed(meta_np, budget_s=0.05):
 
 
 class SynthGraphs:
+    """Free-running synthesis through captured graphs (module docstring).
+
+    Controls: each of ``p_control`` / ``e_control`` / ``d_control`` is a Python number or a control
+    map (a float tensor on the model's device that broadcasts to [B, max_src_len]; see
+    runtime.prosody_controls). A number is a kernel argument baked into the captured graph, so its
+    value is part of the stage-1 key: every new value is a new capture, and a serving loop whose
+    users dial speed or pitch churns through ``max_stage1`` entries. A map lives in device memory:
+    the key holds a marker, the graph reads a static f32 [B, L] buffer filled by the same one-launch
+    copy as the other inputs, and one graph per (B, L) serves every map. A serving loop that wants
+    free scalar changes passes ``torch.full((B, 1), v, device=...)`` instead of ``v``. Stage 2 never
+    reads a map (frame-level variance takes none)."""
+
     def __init__(self, model, max_stage2=16, max_stage1=4, t_step=64, speculate=None, history=8):
         self.model = model
         self.max_stage2 = max_stage2
@@ -123,7 +135,7 @@ class SynthGraphs:
                     texts=i64(texts), src_lens=i64(src_lens), p_targets=f32(p_targets), e_targets=f32(e_targets))
 
     def _stage1_body(self, P, va, s, Lx, controls):
-        p_c, e_c, d_c = controls
+        p_c, e_c, d_c = controls  # numbers, or the static [B, L] control-map buffers
         g = SimpleNamespace(speakers=s["speakers"], emotions=s["emotions"], arousals=s["arousals"],
                             valences=s["valences"], texts=s["texts"], lens_src=s["src_lens"], Lx=Lx,
                             p_targets=s["p_targets"], e_targets=s["e_targets"], d_targets=None, mel_lens=None,
@@ -133,7 +145,7 @@ class SynthGraphs:
             # the first encoder block's launch builds its input and writes the source mask
             src_masks = torch.empty(s["texts"].shape[0], Lx, device=s["texts"].device, dtype=torch.bool)
             g.mask_out = (src_masks, None, None)
-        st = R._stage1(P, va, g, p_c, d_c)
+        st = R._stage1(P, va, g, p_c, d_c, e_control=e_c)
         if R.packed_stage2_ok(P, st, st.x) and R.lr_proj_ok(P, st.x):
             # the decoder's first Q|K|V on the phoneme rows does not depend on T: it runs here,
             # under the host read, instead of opening stage 2
@@ -168,10 +180,19 @@ class SynthGraphs:
         B, Lx = texts.shape[0], int(max_src_len)
         if texts.shape[1] != Lx or B == 0:
             raise RuntimeError(f"SynthGraphs: texts {tuple(texts.shape)} vs max_src_len {Lx}")
-        controls = (float(p_control), float(e_control), float(d_control))
+        # numbers stay numbers (and keep their value in the key); maps become f32 [B, Lx] tensors
+        p_c, e_c, d_c = R.prosody_controls(va, p_control, e_control, d_control, B, Lx, dev)
+        kc = lambda c: "map" if torch.is_tensor(c) else float(c)
         x = self._inputs(dev, speakers, emotions, arousals, valences, texts, src_lens, p_targets, e_targets)
-        key1 = (model._precision, model._vp_precision, B, Lx, controls,
+        key1 = (model._precision, model._vp_precision, B, Lx, (kc(p_control), kc(e_control), kc(d_control)),
                 tuple(k for k, v in x.items() if v is None))
+        if getattr(va, "separate_energy_control", False):
+            key1 += ("separate_energy",)
+        # mapped controls are graph inputs like the batch: a static buffer each, filled by the copy below
+        maps = {"p_control": p_c, "d_control": d_c}
+        if e_c is not p_c:
+            maps["e_control"] = e_c
+        x.update({k: v for k, v in maps.items() if torch.is_tensor(v)})
         ops.bad_id_counter(dev)  # allocated outside any capture
         e1 = self._g1.get(key1)
         if e1 is not None and e1.P is not P:
@@ -181,10 +202,13 @@ class SynthGraphs:
             e1 = None
         if e1 is None:
             static = {k: (None if v is None else v.clone()) for k, v in x.items()}
+            sp, sd = static.get("p_control", p_c), static.get("d_control", d_c)
+            controls = (sp, sp if e_c is p_c else static.get("e_control", e_c), sd)
             graph, (g, st, src_masks, meta) = self._capture(lambda: self._stage1_body(P, va, static, Lx, controls))
             meta_host = torch.empty(meta.shape, dtype=meta.dtype, pin_memory=True)
             e1 = self._g1[key1] = SimpleNamespace(graph=graph, static=static, g=g, st=st, src_masks=src_masks,
-                                                  meta=meta, meta_host=meta_host, meta_np=meta_host.numpy(), P=P)
+                                                  meta=meta, meta_host=meta_host, meta_np=meta_host.numpy(), P=P,
+                                                  controls=controls)
             while len(self._g1) > self.max_stage1:
                 self._drop_stage1(next(iter(self._g1)))
         else:
@@ -256,7 +280,8 @@ class SynthGraphs:
             e2 = None
         if e2 is None:
             def body():
-                mel, post, st2 = R._stage2(P, e1.g, st, T_out, T_out, controls[0], pn_valid, sum_len)
+                mel, post, st2 = R._stage2(P, e1.g, st, T_out, T_out, e1.controls[0], pn_valid, sum_len,
+                                           e_control=e1.controls[1])
                 return mel, post, R._mask(st2.mel_len, T_out)
             graph, outs = self._capture(body)
             e2 = self._g2[key2] = SimpleNamespace(graph=graph, graph_b=None, outs=outs, e1=e1)

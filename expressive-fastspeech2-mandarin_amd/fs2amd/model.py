@@ -134,6 +134,10 @@ class _VarianceAdaptor(nn.Module):
         self.length_regulator = LengthRegulator()
         self.pitch_predictor = _VariancePredictor(cfg)
         self.energy_predictor = _VariancePredictor(cfg)
+        # model config variance_adaptor.separate_energy_control (default False: the reference scales
+        # energy by p_control and ignores e_control, modules.py:124-125); True: energy is scaled by
+        # e_control (a number or a control map)
+        self.separate_energy_control = bool((cfg.get("variance_adaptor") or {}).get("separate_energy_control", False))
         self.pitch_feature_level = pcfg["preprocessing"]["pitch"]["feature"]
         self.energy_feature_level = pcfg["preprocessing"]["energy"]["feature"]
         assert self.pitch_feature_level in ["phoneme_level", "frame_level"]

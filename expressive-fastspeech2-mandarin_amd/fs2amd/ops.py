@@ -49,6 +49,27 @@ def _gpu(*ts):
                                "there is no CPU fallback")
 
 
+def control_arg(control, B, Lx, device, name="control"):
+    """A pitch / energy / duration control as the kernels take it: a Python number -> (float, None),
+    the scalar entry points; a control map -> (1.0, f32 [B, Lx] contiguous on ``device``), the
+    ``*_map`` entry points of include/fs2hip_prosody.h. A control map is a float tensor that
+    broadcasts to [B, Lx] under torch's rules (0-dim, [1], [Lx], [B, 1], [1, Lx], [B, Lx]); a
+    contiguous f32 [B, Lx] map is passed through as it is (no copy), anything else costs one small
+    copy. Maps must be finite; the values in padded slots do not matter (0 * c = 0)."""
+    if not torch.is_tensor(control):
+        return float(control), None
+    if not control.is_floating_point():
+        raise ValueError(f"fs2amd: {name} map must be a float tensor, got {control.dtype}")
+    if control.dim() > 2 or any(a not in (1, b) for a, b in zip(((1, 1) + tuple(control.shape))[-2:], (B, Lx))):
+        raise ValueError(f"fs2amd: {name} map of shape {tuple(control.shape)} does not broadcast to "
+                         f"[B, max_src_len] = [{B}, {Lx}]")
+    device = torch.device(device)
+    if control.device.type != device.type or (device.index is not None and control.device.index != device.index):
+        raise RuntimeError(f"fs2amd: {name} map is on {control.device} but the HIP kernels run on {device}; move it "
+                           f"there (there is no CPU fallback)")
+    return 1.0, control.detach().to(torch.float32).expand(B, Lx).contiguous()
+
+
 def _rows(x, name):
     """Row stride (elements) of a [B, T, C] (or packed [rows, C]) tensor with evenly spaced rows."""
     if x.dim() == 2 and x.stride(1) == 1:
@@ -998,10 +1019,16 @@ def cond_bwd(dy, speakers, spk_table, emotions, arousals, valences, emo_table, a
 
 
 def variance_embed(x, pred, target, control, bins, table):
-    """In place: pred *= control (no target); x += table[bucketize(target or pred, bins)]."""
+    """In place: pred *= control (no target); x += table[bucketize(target or pred, bins)]. control:
+    a number, or a control map broadcastable to pred's [B, L] (control_arg; fs2_variance_embed_map)."""
     _gpu(x, pred, target, bins, table)
     M = pred.numel()
     D = x.shape[-1]
+    if torch.is_tensor(control):
+        c, cmap = control_arg(control, pred.shape[0] if pred.dim() == 2 else 1, pred.shape[-1], pred.device)
+        L.check(_lib.fs2_variance_embed_map(_ptr(x), _dt(x), _ptr(pred), _ptr(target), c, _ptr(cmap), _ptr(bins),
+                                            bins.numel() + 1, _ptr(table), M, D, _stream(x)), "fs2_variance_embed_map")
+        return
     L.check(_lib.fs2_variance_embed(_ptr(x), _dt(x), _ptr(pred), _ptr(target), float(control), _ptr(bins),
                                     bins.numel() + 1, _ptr(table), M, D, _stream(x)), "fs2_variance_embed")
 
@@ -1022,7 +1049,8 @@ def vp_norm(y, gamma, beta, eps, out=None):
 def vp_head(y, gamma, beta, eps, lin_w, lin_b, lens, embed=None):
     """fs2_vp_head: y f32 [B, T, G*256] (relu(conv2)) -> per group LayerNorm, Linear(256->1), masked
     -> pred f32 [G, B, T]. embed = (g, x, target, control, bins, table): group g's value also does
-    the pitch / energy embedding add into x in place (fs2_variance_embed semantics)."""
+    the pitch / energy embedding add into x in place (fs2_variance_embed semantics; control a
+    number, or a control map broadcastable to [B, T]: fs2_vp_head_map)."""
     _gpu(y, gamma, beta, lin_w, lin_b, lens)
     B, T, _ = y.shape
     G = gamma.numel() // 256
@@ -1034,6 +1062,15 @@ def vp_head(y, gamma, beta, eps, lin_w, lin_b, lens, embed=None):
         assert x.shape[:2] == (B, T) and table.shape[1] == x.shape[-1]
         if target is not None:
             assert target.dtype == torch.float32 and target.is_contiguous() and target.numel() == B * T
+    if torch.is_tensor(control):
+        c, cmap = control_arg(control, B, T, y.device)
+        L.check(_lib.fs2_vp_head_map(_ptr(y), _rows(y, "y"), B, T, G, 256, _ptr(gamma), _ptr(beta), float(eps),
+                                     _ptr(lin_w), _ptr(lin_b), _ptr(lens), _ptr(pred), int(eg), _ptr(x),
+                                     _dt(x) if x is not None else 0, _rows(x, "x") if x is not None else 0,
+                                     x.shape[-1] if x is not None else 0, _ptr(target), c, _ptr(cmap), _ptr(bins),
+                                     bins.numel() + 1 if bins is not None else 0, _ptr(table), _stream(y)),
+                "fs2_vp_head_map")
+        return pred
     L.check(_lib.fs2_vp_head(_ptr(y), _rows(y, "y"), B, T, G, 256, _ptr(gamma), _ptr(beta), float(eps), _ptr(lin_w),
                              _ptr(lin_b), _ptr(lens), _ptr(pred), int(eg), _ptr(x), _dt(x) if x is not None else 0,
                              _rows(x, "x") if x is not None else 0, x.shape[-1] if x is not None else 0,
@@ -1065,7 +1102,8 @@ def pack_vp_fused(convs):
 def vp_fused(x, F, lens, embed=None):
     """fs2_vp_fused: F.G VariancePredictors (bf16x3) on bf16 rows x [B, L, 256] in one launch ->
     pred f32 [G, B, L]; embed = (g, target, control, bins, table): group g also writes
-    x_out = x + table[bucketize(...)] (a new tensor; returned as the second value, else None)."""
+    x_out = x + table[bucketize(...)] (a new tensor; returned as the second value, else None).
+    control: a number, or a control map broadcastable to [B, L] (control_arg; fs2_vp_fused_map)."""
     _gpu(x, F.w, F.vec, F.lin_b, lens)
     if x.dtype != torch.bfloat16 or x.shape[-1] != 256:
         raise TypeError("fs2amd.vp_fused: bf16 [B, L, 256] input only")
@@ -1073,7 +1111,12 @@ def vp_fused(x, F, lens, embed=None):
     assert lens.dtype == torch.int64 and lens.numel() == B
     assert F.w.numel() == _lib.fs2_vp_fused_weight_elems(F.G)
     pred = torch.empty(F.G, B, Lx, device=x.device, dtype=torch.float32)
-    d = L.VpFusedDesc()
+    dm = cmap = None
+    if embed is not None and torch.is_tensor(embed[2]):
+        dm = L.VpFusedMapDesc()
+        d = dm.base
+    else:
+        d = L.VpFusedDesc()
     d.x, d.x_row_stride = x.data_ptr(), _rows(x, "x")
     d.w, d.vec, d.lin_b, d.ln_eps = F.w.data_ptr(), F.vec.data_ptr(), F.lin_b.data_ptr(), float(F.eps)
     d.B, d.L, d.G = B, Lx, F.G
@@ -1088,9 +1131,15 @@ def vp_fused(x, F, lens, embed=None):
         x_out = torch.empty_like(x)
         d.embed_group = int(g)
         d.x_out, d.x_out_row_stride = x_out.data_ptr(), 256
+        if dm is not None:
+            control, cmap = control_arg(control, B, Lx, x.device)
+            dm.control_map = cmap.data_ptr()
         d.target, d.control = (target.data_ptr() if target is not None else None), float(control)
         d.bins, d.n_bins, d.table = bins.data_ptr(), bins.numel() + 1, table.data_ptr()
-    L.check(_lib.fs2_vp_fused(ctypes.byref(d), _stream(x)), "fs2_vp_fused")
+    if dm is not None:
+        L.check(_lib.fs2_vp_fused_map(ctypes.byref(dm), _stream(x)), "fs2_vp_fused_map")
+    else:
+        L.check(_lib.fs2_vp_fused(ctypes.byref(d), _stream(x)), "fs2_vp_fused")
     return pred, x_out
 
 
@@ -1152,13 +1201,20 @@ def len_stats(lens, bad=None):
 
 
 def lr_durations(dur, logpred=False, d_control=1.0):
-    """Frame counts -> (cum int32 [B, L], mel_len int64 [B], d_rounded f32 [B, L] or None)."""
+    """Frame counts -> (cum int32 [B, L], mel_len int64 [B], d_rounded f32 [B, L] or None).
+    d_control: a number, or (log-duration predictions only) a control map broadcastable to [B, L]
+    (control_arg; fs2_lr_durations_map)."""
     _gpu(dur)
     dur = dur.contiguous()
     B, Lx = dur.shape
     cum = torch.empty(B, Lx, device=dur.device, dtype=torch.int32)
     mel_len = torch.empty(B, device=dur.device, dtype=torch.int64)
     d_rounded = torch.empty(B, Lx, device=dur.device, dtype=torch.float32) if logpred else None
+    if torch.is_tensor(d_control):
+        c, dmap = control_arg(d_control, B, Lx, dur.device, "d_control")
+        L.check(_lib.fs2_lr_durations_map(_ptr(dur), _dur_kind(dur, logpred), c, _ptr(dmap), B, Lx, _ptr(cum),
+                                          _ptr(mel_len), _ptr(d_rounded), _stream(dur)), "fs2_lr_durations_map")
+        return cum, mel_len, d_rounded
     L.check(_lib.fs2_lr_durations(_ptr(dur), _dur_kind(dur, logpred), float(d_control), B, Lx, _ptr(cum),
                                   _ptr(mel_len), _ptr(d_rounded), _stream(dur)), "fs2_lr_durations")
     return cum, mel_len, d_rounded
@@ -1227,7 +1283,8 @@ def lr_fused(x, lens, T_out, pe=None, out_dtype=None, dur=None, logpred=False, d
     returns (out, layout, cum, mel_len, d_rounded)) or from fs2_lr_durations (``cum``, ``mel_len``:
     returns (out, layout)). ``proj`` = (proj_src f32 [B*Lx, NP], proj_pe f32 [>= T_out, NP])
     (fs2_lr_fused_proj): the packed bf16 rows bf16(proj_src[src] + proj_pe[t]) come back as one
-    more trailing result."""
+    more trailing result. d_control: a number, or (``dur`` log-duration predictions only) a control
+    map broadcastable to [B, L] (control_arg; fs2_lr_fused_proj_map)."""
     _gpu(x, lens, pe, dur, cum, mel_len)
     x = x.contiguous()
     B, Lx, D = x.shape
@@ -1251,6 +1308,15 @@ def lr_fused(x, lens, T_out, pe=None, out_dtype=None, dur=None, logpred=False, d
         cum = torch.empty(B, Lx, device=dev, dtype=torch.int32)
         mel_len = torch.empty(B, device=dev, dtype=torch.int64)
         d_rounded = torch.empty(B, Lx, device=dev, dtype=torch.float32) if logpred else None
+        if torch.is_tensor(d_control):
+            c, dmap = control_arg(d_control, B, Lx, dev, "d_control")
+            L.check(_lib.fs2_lr_fused_proj_map(_ptr(x), _dt(x), _ptr(dur), _dur_kind(dur, logpred), c, _ptr(dmap), None,
+                                               None, B, Lx, D, int(T_out), _ptr(pe), _ptr(lens), _ptr(lay.cu),
+                                               _ptr(lay.row_pos), _ptr(lay.rowmap), _ptr(out), od, _ptr(cum),
+                                               _ptr(mel_len), _ptr(d_rounded), _ptr(psrc), _ptr(ppe), NP, _ptr(pout),
+                                               _stream(x)), "fs2_lr_fused_proj_map")
+            res = (out, lay, cum, mel_len, d_rounded)
+            return res + (pout,) if proj is not None else res
         L.check(_lib.fs2_lr_fused_proj(_ptr(x), _dt(x), _ptr(dur), _dur_kind(dur, logpred), float(d_control), None,
                                        None, B, Lx, D, int(T_out), _ptr(pe), _ptr(lens), _ptr(lay.cu),
                                        _ptr(lay.row_pos), _ptr(lay.rowmap), _ptr(out), od, _ptr(cum), _ptr(mel_len),
@@ -1258,6 +1324,8 @@ def lr_fused(x, lens, T_out, pe=None, out_dtype=None, dur=None, logpred=False, d
                 "fs2_lr_fused_proj")
         res = (out, lay, cum, mel_len, d_rounded)
     else:
+        if torch.is_tensor(d_control):
+            raise ValueError("fs2amd.lr_fused: a d_control map needs the durations (dur=..., logpred=True)")
         L.check(_lib.fs2_lr_fused_proj(_ptr(x), _dt(x), None, 0, 1.0, _ptr(cum), _ptr(mel_len), B, Lx, D, int(T_out),
                                        _ptr(pe), _ptr(lens), _ptr(lay.cu), _ptr(lay.row_pos), _ptr(lay.rowmap),
                                        _ptr(out), od, None, None, None, _ptr(psrc), _ptr(ppe), NP, _ptr(pout),
@@ -1266,13 +1334,20 @@ def lr_fused(x, lens, T_out, pe=None, out_dtype=None, dur=None, logpred=False, d
     return res + (pout,) if proj is not None else res
 
 
-def length_regulate(x, duration, max_len=None, return_index_map=False):
+def length_regulate(x, duration, max_len=None, return_index_map=False, d_control=None):
     """Drop-in for the reference ``LengthRegulator.forward(x, duration, max_len)``
     (model/modules.py:192-194): returns (output [B, T, D], mel_len int64 [B]).
 
     T = max_len when given (and non-zero, like utils/tools.py:361), else max(mel_len) — the
     one device->host read this path needs. With max_len the whole op is ONE fs2_length_regulate
-    launch (scan + gather + zero padding)."""
+    launch (scan + gather + zero padding).
+
+    d_control (a number or a control map broadcastable to [B, L], control_arg): the log-pred form --
+    ``duration`` holds f32 log-duration predictions, rounded and scaled like modules.py:132-135
+    (d_rounded = clamp(round(exp(d) - 1) * d_control, min=0)); d_rounded [B, L] f32 is then
+    returned as one more trailing result. Same launches as without it."""
+    if d_control is not None:
+        return _length_regulate_logpred(x, duration, max_len, return_index_map, d_control)
     if max_len:
         _gpu(x, duration)
         x, duration = x.contiguous(), duration.contiguous()
@@ -1292,6 +1367,32 @@ def length_regulate(x, duration, max_len=None, return_index_map=False):
     if return_index_map:
         return res[0], mel_len, res[1]
     return res, mel_len
+
+
+def _length_regulate_logpred(x, log_d, max_len, return_index_map, d_control):
+    _gpu(x, log_d)
+    x, log_d = x.contiguous(), log_d.contiguous()
+    if log_d.dtype != torch.float32:
+        raise TypeError(f"fs2amd.length_regulate: log-duration predictions must be float32, got {log_d.dtype}")
+    B, Lx, D = x.shape
+    if max_len:
+        T_out = int(max_len)
+        c, dmap = control_arg(d_control, B, Lx, x.device, "d_control")
+        cum = torch.empty(B, Lx, device=x.device, dtype=torch.int32)
+        mel_len = torch.empty(B, device=x.device, dtype=torch.int64)
+        d_rounded = torch.empty(B, Lx, device=x.device, dtype=torch.float32)
+        out = torch.empty(B, T_out, D, device=x.device, dtype=x.dtype)
+        im = torch.empty(B, T_out, device=x.device, dtype=torch.int32) if return_index_map else None
+        L.check(_lib.fs2_length_regulate_map(_ptr(x), _dt(x), _ptr(log_d), L.DUR_LOGPRED, c, _ptr(dmap), B, Lx, D,
+                                             T_out, None, _ptr(out), _dt(x), _ptr(cum), _ptr(mel_len), _ptr(d_rounded),
+                                             _ptr(im), _stream(x)), "fs2_length_regulate_map")
+        return (out, mel_len, im, d_rounded) if return_index_map else (out, mel_len, d_rounded)
+    cum, mel_len, d_rounded = lr_durations(log_d, logpred=True, d_control=d_control)
+    T_out = int(mel_len.max().item()) if mel_len.numel() else 0
+    res = lr_expand(x, cum, mel_len, T_out, index_map=return_index_map)
+    if return_index_map:
+        return res[0], mel_len, res[1], d_rounded
+    return res, mel_len, d_rounded
 
 
 # ---- training-step kernels (train.hip) ------------------------------------------------------------

@@ -436,6 +436,30 @@ def _device_ok(dev):
     return dev.type == "cuda"
 
 
+def prosody_controls(va, p_control, e_control, d_control, B, Lx, dev):
+    """The three controls of a forward call as the kernels take them: (pitch, energy, duration),
+    each a Python float (the scalar entry points, as ever) or a control map normalised by
+    ops.control_arg to a contiguous f32 [B, Lx] tensor on ``dev`` (a float tensor that broadcasts
+    to [B, max_src_len] gives each phoneme its own factor, as the reference's broadcast does,
+    model/modules.py:80-100,117-135).
+
+    Energy follows the reference (modules.py:124-125): it is scaled by p_control and e_control is
+    accepted and ignored -- unless the VarianceAdaptor's ``separate_energy_control`` is set
+    (model config ``variance_adaptor.separate_energy_control``), which scales energy by e_control.
+    A per-phoneme map has no meaning for a frame-level feature: with frame-level pitch or energy a
+    pitch / energy map raises ValueError (a d_control map is still fine)."""
+    separate = bool(getattr(va, "separate_energy_control", False))
+    frame_level = "frame_level" in (va.pitch_feature_level, va.energy_feature_level)
+    if frame_level and (torch.is_tensor(p_control) or (separate and torch.is_tensor(e_control))):
+        raise ValueError("fs2amd: a per-phoneme pitch / energy control map needs phoneme-level pitch and energy "
+                         "(preprocessing.*.feature is frame_level); pass a number")
+    norm = lambda c, name: ops.control_arg(c, B, Lx, dev, name)
+    p = norm(p_control, "p_control")
+    e = norm(e_control, "e_control") if separate else p
+    d = norm(d_control, "d_control")
+    return tuple(c if m is None else m for c, m in (p, e, d))
+
+
 def _streams_for(B):
     """Utterance groups run as parallel HIP streams (parallel branches of a captured graph): one
     group's partial last wave of workgroups and its launch ramps overlap the other group's work.
@@ -496,10 +520,13 @@ class _ForkJoin:
                     t.record_stream(self.main)
 
 
-def _stage1(P, va, g, p_control, d_control, defer_lr=False):
+def _stage1(P, va, g, p_control, d_control, defer_lr=False, e_control=None):
     """Encoder (+ conditioning), variance predictors, duration scan for one utterance group.
     defer_lr (teacher-forced durations, decoder length known): the duration scan is left to the
-    one-launch LengthRegulator of stage 2 (fs2_lr_fused)."""
+    one-launch LengthRegulator of stage 2 (fs2_lr_fused). The controls are numbers or [B, L] maps
+    (prosody_controls); e_control None: energy is scaled by p_control (modules.py:124-125)."""
+    if e_control is None:
+        e_control = p_control
     fold = getattr(g, "mask_out", None) is not None
     if not fold:
         x = ops.embed_pe(g.texts, P.enc_emb, _pe(P, "enc", g.Lx), P.act_dtype)
@@ -560,8 +587,8 @@ def _stage1(P, va, g, p_control, d_control, defer_lr=False):
             dp, x = ops.vp_fused(x, V.dp, g.lens_src, embed=(1, g.p_targets, p_control, P.bins["pitch"],
                                                                P.var_table["pitch"]))
             st.log_d, st.p_pred = dp[0], dp[1]
-            en, x = ops.vp_fused(x, V.energy, g.lens_src, embed=(0, g.e_targets, p_control, P.bins["energy"],
-                                                                 P.var_table["energy"]))  # p_control: :124-125
+            en, x = ops.vp_fused(x, V.energy, g.lens_src, embed=(0, g.e_targets, e_control, P.bins["energy"],
+                                                                 P.var_table["energy"]))  # = p_control: :124-125
         st.e_pred = en[0]
         st.x = x
     elif P.vpcols is not None and st.phoneme_p and st.phoneme_e and vp_columns_on():
@@ -572,13 +599,13 @@ def _stage1(P, va, g, p_control, d_control, defer_lr=False):
                                  embed=(1, x, g.p_targets, p_control, P.bins["pitch"], P.var_table["pitch"]))
         st.log_d, st.p_pred = dp[0], dp[1]
         st.e_pred = variance_predictors(V.energy, x, g.lens_src, embed=(
-            0, x, g.e_targets, p_control, P.bins["energy"], P.var_table["energy"]))[0]  # p_control: :124-125
+            0, x, g.e_targets, e_control, P.bins["energy"], P.var_table["energy"]))[0]  # = p_control: :124-125
     else:
         st.log_d = variance_predictor(P.vp["duration"], x, g.lens_src)
     if st.phoneme_p and st.p_pred is None:
         st.p_pred = _variance(P, "pitch", x, g.lens_src, g.p_targets, p_control)
     if st.phoneme_e and st.e_pred is None:
-        st.e_pred = _variance(P, "energy", x, g.lens_src, g.e_targets, p_control)  # p_control: modules.py:124-125
+        st.e_pred = _variance(P, "energy", x, g.lens_src, g.e_targets, e_control)  # = p_control: modules.py:124-125
     if g.d_targets is not None:
         st.d_rounded = None
         if defer_lr:
@@ -610,8 +637,11 @@ def lr_fused_ok(x):
     return lr_fused_on() and x.shape[1] <= 2048 and x.shape[0] <= 4096
 
 
-def _stage2(P, g, st, T_out, T_dec, p_control, postnet_valid=False, rows_hint=None):
-    """LengthRegulator gather, decoder, mel_linear, PostNet for one utterance group."""
+def _stage2(P, g, st, T_out, T_dec, p_control, postnet_valid=False, rows_hint=None, e_control=None):
+    """LengthRegulator gather, decoder, mel_linear, PostNet for one utterance group. The controls
+    (numbers: frame-level variance takes no map) are read by the frame-level predictors only."""
+    if e_control is None:
+        e_control = p_control
     dec_lens = st.mel_len if g.d_targets is None else g.mel_lens
     frame_level = not (st.phoneme_p and st.phoneme_e)
     x = st.x
@@ -629,7 +659,7 @@ def _stage2(P, g, st, T_out, T_dec, p_control, postnet_valid=False, rows_hint=No
         if not st.phoneme_p:
             st.p_pred = _variance(P, "pitch", x, dec_lens, g.p_targets, p_control)
         if not st.phoneme_e:
-            st.e_pred = _variance(P, "energy", x, dec_lens, g.e_targets, p_control)
+            st.e_pred = _variance(P, "energy", x, dec_lens, g.e_targets, e_control)
         x = x[:, :T_dec].contiguous()
         x = _add_pe(x, _pe(P, "dec", T_dec))
     else:
@@ -752,6 +782,7 @@ def run_forward(model, speakers, emotions, arousals, valences, texts, src_lens, 
     if texts.shape[1] != Lx:
         raise RuntimeError(f"texts has {texts.shape[1]} positions but max_src_len is {Lx}")
     src_lens = src_lens.to(dev)
+    p_control, e_control, d_control = prosody_controls(va, p_control, e_control, d_control, B, Lx, dev)
     n = _streams_for(B)
     mel_w = None if mel_lens is None else (max_mel_len if max_mel_len is not None else int(mel_lens.max().item()))
     mask_out = None
@@ -779,6 +810,8 @@ def run_forward(model, speakers, emotions, arousals, valences, texts, src_lens, 
         return SimpleNamespace(**{k: (sl(v) if torch.is_tensor(v) else v) for k, v in vars(full).items()})
 
     groups = [part(b0, b1) for b0, b1 in bounds] if n > 1 else [full]
+    # a group's rows of a control map (rows of a contiguous [B, L] map: contiguous again)
+    ctl = lambda c, i: c[bounds[i][0]:bounds[i][1]] if torch.is_tensor(c) else c
     fj = _ForkJoin(dev, n)
     fj.fork()
     sts = []
@@ -787,7 +820,8 @@ def run_forward(model, speakers, emotions, arousals, valences, texts, src_lens, 
     defer = d_targets is not None and bool(max_mel_len)
     for i, g in enumerate(groups):
         with fj.ctx(i):
-            sts.append(_stage1(P, va, g, p_control, d_control, defer_lr=defer))
+            sts.append(_stage1(P, va, g, ctl(p_control, i), ctl(d_control, i), defer_lr=defer,
+                               e_control=ctl(e_control, i)))
 
     mel_len = sts[0].mel_len if n == 1 else None
     if not max_mel_len or d_targets is None:
@@ -824,7 +858,7 @@ def run_forward(model, speakers, emotions, arousals, valences, texts, src_lens, 
     for i, (g, st) in enumerate(zip(groups, sts)):
         with fj.ctx(i):
             res.append(_stage2(P, g, st, T_out, T_dec, p_control, pn_valid,
-                               sum_len if (d_targets is None and n == 1) else None))
+                               sum_len if (d_targets is None and n == 1) else None, e_control=e_control))
     if n == 1:
         mel, postnet_mel, st = res[0]
         out = (mel, postnet_mel, st.p_pred, st.e_pred, st.log_d, st.d_rounded, st.mel_len)

@@ -812,6 +812,11 @@ def train_forward(model, speakers, emotions, arousals, valences, texts, src_lens
     enc, dec, va = model.encoder, model.decoder, model.variance_adaptor
     src_lens = src_lens.to(dev)
     B, Lx = texts.shape
+    from .runtime import prosody_controls
+
+    # numbers, or per-phoneme control maps as f32 [B, Lx] (the torch ops below broadcast either);
+    # e_control: p_control unless the adaptor's separate_energy_control is set (modules.py:124-125)
+    p_control, e_control, d_control = prosody_controls(va, p_control, e_control, d_control, B, int(max_src_len), dev)
     src_masks = _mask(src_lens, max_src_len)
     if mel_lens is not None:  # get_mask_from_lengths falls back to max(lengths) (utils/tools.py:153-155)
         mel_masks = _mask(mel_lens, max_mel_len if max_mel_len is not None else int(mel_lens.max().item()))
@@ -863,7 +868,7 @@ def train_forward(model, speakers, emotions, arousals, valences, texts, src_lens
     if va.pitch_feature_level == "phoneme_level":
         p_pred, x = _variance_embed(va, "pitch", x, p_targets, src_masks, p_control, training, compute, vseed, 1002)
     if va.energy_feature_level == "phoneme_level":
-        e_pred, x = _variance_embed(va, "energy", x, e_targets, src_masks, p_control, training, compute, vseed,
+        e_pred, x = _variance_embed(va, "energy", x, e_targets, src_masks, e_control, training, compute, vseed,
                                       1004)
     # phoneme-level variance (this config): the decoder crop and its position encoding join the
     # LengthRegulator's gather (one pass); frame-level variance needs the bare expanded x first
@@ -881,7 +886,7 @@ def train_forward(model, speakers, emotions, arousals, valences, texts, src_lens
         p_pred, x = _variance_embed(va, "pitch", x, p_targets, mel_masks, p_control, training, compute, vseed,
                                       1002)
     if va.energy_feature_level == "frame_level":
-        e_pred, x = _variance_embed(va, "energy", x, e_targets, mel_masks, p_control, training, compute, vseed,
+        e_pred, x = _variance_embed(va, "energy", x, e_targets, mel_masks, e_control, training, compute, vseed,
                                       1004)
 
     # decoder (transformer/Models.py:139-171, training: crop to max_seq_len)
