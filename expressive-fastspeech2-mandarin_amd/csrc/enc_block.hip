@@ -19,6 +19,8 @@
 // q / k / v / o round exactly as the three-launch path does. Phase 3: wave w computes fc columns
 // 32w .. 32w+31, then + bfc + x, LayerNorm statistics over the 8 waves through LDS, the row mask,
 // and whole-row stores through an LDS staging tile.
+#include <cstdlib>
+
 #include "cond.h"
 #include "fs2_common.h"
 
@@ -29,6 +31,10 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int D = 256, NQKV = 768, LMAX = 64, DK = 128, NT = 512;
 constexpr int kUnit = 4096;  // fragment-order unit: 64 weight rows x 32 channels
+// row-split form (enc_attn_rows_kernel) while its 4 B workgroups fit ONE round of the 256 CUs: a second
+// round repeats the whole prologue + weight stream (graph-timed us per launch, one workgroup per
+// utterance / row-split: B = 64 14.5 / 10.3, B = 128 15.4 / 19.6, B = 256 18.4 / 17.8)
+constexpr int kRowsMaxB = 64;
 
 __device__ __forceinline__ rsrc_t rsrc(const void *p, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, (int)bytes, 0x00020000);
@@ -833,6 +839,349 @@ __global__ __launch_bounds__(NT, 1) void enc_attn_half_kernel(EncBlockArgs p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Row-split form: FOUR workgroups per utterance, workgroup (b, q) owning query rows 16 q .. 16 q + 15.
+// Each computes K and V for all 64 rows of the utterance (the redundant projection, ~17 MFLOP, buys
+// independence: no hand-off, no counter) and Q for its own 16 rows, runs the attention of its 16
+// queries (wave h < 2 = head h) and the fc GEMM, LayerNorm and stores of its 16 rows. One workgroup
+// per utterance keeps 64 of 256 CUs busy on a latency chain (prologue, Q|K|V, its epilogue,
+// attention, fc, LayerNorm); here the Q|K|V epilogue shrinks by a quarter and fc / LayerNorm / the
+// stores to a quarter, on 4 B CUs. Every accumulator keeps enc_attn_block_kernel's k order and the
+// LayerNorm its partial grouping (8 waves x 32 columns, combined in the same order), so the output
+// is bit-identical; a quarter with no valid row writes zero rows (there the one-workgroup form
+// multiplies the normalised row by 0). The 4 quarters of an utterance are adjacent in the XCD-aware
+// order of ffn_wide.hip (grid padded to a multiple of 32), so its x rows and the weights stay in one L2.
+template <bool EMBED>
+__global__ __launch_bounds__(NT, 1) void enc_attn_rows_kernel(EncBlockArgs p) {
+  __shared__ __attribute__((aligned(16))) char smem[SMEM];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, li = lane & 15;
+  const int bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int b = bid >> 2, q = bid & 3, L = p.L;
+  if (b >= p.B || 16 * q >= L) return;
+  const int64_t len64 = p.lens[b];
+  const int len = (int)(len64 < 0 ? 0 : (len64 > L ? L : len64));
+  const uint32_t xrow0 = (uint32_t)b * (uint32_t)L;
+  const int nrow = min(16, L - 16 * q);  // this quarter's rows inside [0, L)
+  uint4 *orow = reinterpret_cast<uint4 *>(p.out + ((size_t)xrow0 + 16 * q) * D);
+
+  if constexpr (EMBED) {
+    // quarter 0 alone writes the masks (get_mask_from_lengths, utils/tools.py:152-160: True = padding)
+    if (q == 0) {
+      if (p.src_mask != nullptr)
+        for (int t = tid; t < L; t += NT) p.src_mask[(int64_t)b * L + t] = (int64_t)t >= len64 ? 1 : 0;
+      if (p.mel_mask != nullptr) {
+        const int64_t ml = p.mel_lens[b];
+        for (int t = tid; t < p.T_mel; t += NT) p.mel_mask[(int64_t)b * p.T_mel + t] = (int64_t)t >= ml ? 1 : 0;
+      }
+    }
+  }
+  if (16 * q >= len) {  // no valid row: zero rows only
+    if constexpr (EMBED) {
+      // (quarter 0 of an empty utterance: it still counts the utterance's out-of-vocabulary ids)
+      if (q == 0 && p.bad != nullptr && tid < L) {
+        const int64_t tok = p.tokens[xrow0 + tid];
+        if (tok < 0 || tok >= p.vocab) atomicAdd(p.bad, 1);
+      }
+    }
+    if (tid < nrow * 32) orow[tid] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+
+  // ---- x tile (all 64 rows: K and V need them; rows >= L zeros) and the four vectors by LDS-DMA
+  if constexpr (!EMBED) {
+    const rsrc_t xr = rsrc(p.x, (uint32_t)p.B * (uint32_t)L * D * 2u);
+    for (int pc = w; pc < LMAX * XP / 1024; pc += 8) {
+      const int o = pc * 1024 + lane * 16, r = o / XP, within = o - r * XP;
+      const bool ok = r < L && within < D * 2;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void *)(smem + X_OFF + pc * 1024),
+                                               16, ok ? (xrow0 + r) * (uint32_t)(D * 2) + (uint32_t)within : 0x80000000u,
+                                               0, 0, 0);
+    }
+  }
+  if (w < 6) {
+    const float *src = w < 3 ? p.bqkv + 256 * w : w == 3 ? p.bfc : w == 4 ? p.gamma : p.beta;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc(src, 1024), (__attribute__((address_space(3))) void *)(smem + VEC_OFF + w * 1024),
+                                             16, (uint32_t)lane * 16u, 0, 0, 0);
+  }
+  const float *vqkv = reinterpret_cast<const float *>(smem + VEC_OFF);
+  const float *vfc = vqkv + NQKV, *vg = vfc + D, *vb = vg + D;
+
+  // ---- phase 1: K | V for 64 rows (wave w: blocks 16 + 4 w + i, i < 4) and Q for rows 16 q .. (blocks
+  // 2 w + i, i < 2): 6 weight fragments per k-step, as the one-workgroup form's ring
+  constexpr int NKV = 4, NQ = 2, NB1 = NKV + NQ, RING = 4;
+  const rsrc_t wq = rsrc(p.wqkv, (uint32_t)NQKV * D * 2u);
+  bf16x8 ring[RING][NB1];
+  auto gblock = [&](int i) { return i < NKV ? 16 + NKV * w + i : NQ * w + (i - NKV); };
+  auto wload = [&](int ks, bf16x8 (&dst)[NB1]) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < NB1; ++i) {
+      const int nb = gblock(i);
+      auto v = __builtin_amdgcn_raw_buffer_load_b128(
+          wq, (uint32_t)lane * 16u + (uint32_t)(nb & 3) * 1024u, (uint32_t)(((nb >> 2) * (D / 32) + ks) * kUnit), 0);
+      dst[i] = __builtin_bit_cast(bf16x8, v);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+#pragma unroll
+  for (int ks = 0; ks < RING; ++ks) wload(ks, ring[ks]);
+  if constexpr (EMBED) {
+    // x rows as enc_attn_block_kernel builds them; quarter 0 counts the out-of-vocabulary ids
+    for (int i = tid; i < LMAX * (D / 8); i += NT) {
+      const int r = i >> 5, c = (i & 31) * 8;
+      bf16x8 o;
+      if (r < L) {
+        const int64_t tok = p.tokens[xrow0 + r];
+        if (tok < 0 || tok >= p.vocab) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) o[k] = (bf16)__builtin_nanf("");
+          if (p.bad != nullptr && c == 0 && q == 0) atomicAdd(p.bad, 1);
+        } else {
+          float v[8], e[8];
+          load8(p.emb + tok * D + c, v);
+          load8(p.pe + (int64_t)r * D + c, e);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) o[k] = (bf16)(v[k] + e[k]);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (bf16)0.f;
+      }
+      *reinterpret_cast<bf16x8 *>(smem + X_OFF + r * XP + c * 2) = o;
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING - 1) * NB1) : "memory");
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  bar();
+
+  f32x4 acc[NKV][4], qacc[NQ];
+#pragma unroll
+  for (int i = 0; i < NKV; ++i)
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) acc[i][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) qacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int mq = 16 * q + li;  // this lane's row of the quarter
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) {
+    bf16x8 xf[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+      xf[mb] = *reinterpret_cast<const bf16x8 *>(smem + X_OFF + (16 * mb + li) * XP + ks * 64 + g * 16);
+    const bf16x8 xq = *reinterpret_cast<const bf16x8 *>(smem + X_OFF + mq * XP + ks * 64 + g * 16);
+#pragma unroll
+    for (int i = 0; i < NKV; ++i)
+#pragma unroll
+      for (int mb = 0; mb < 4; ++mb)
+        acc[i][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % RING][i], xf[mb], acc[i][mb], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i)
+      qacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % RING][NKV + i], xq, qacc[i], 0, 0, 0);
+    if (ks + RING < D / 32) wload(ks + RING, ring[ks % RING]);
+  }
+  // + bias, bf16: K / V in attention.hip's swizzled image, Q row-major (rows 16 q .. only)
+#pragma unroll
+  for (int i = 0; i < NKV; ++i) {
+    const int n = 16 * gblock(i) + 4 * g;
+    const float4 bb = *reinterpret_cast<const float4 *>(vqkv + n);
+    const int part = n >> 8, hh = (n >> 7) & 1, dim = n & 127;  // part 1 K, 2 V
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+      const int m = 16 * mb + li;
+      const f32x4 v = acc[i][mb];
+      const bf16x4 o = {(bf16)(v[0] + bb.x), (bf16)(v[1] + bb.y), (bf16)(v[2] + bb.z), (bf16)(v[3] + bb.w)};
+      *reinterpret_cast<bf16x4 *>(smem + (part == 1 ? K_OFF : V_OFF) + hh * LMAX * 256 + kv_off(m, dim >> 3) + (dim & 7) * 2) = o;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int n = 16 * gblock(NKV + i) + 4 * g;
+    const float4 bb = *reinterpret_cast<const float4 *>(vqkv + n);
+    const int hh = (n >> 7) & 1, dim = n & 127;
+    const f32x4 v = qacc[i];
+    const bf16x4 o = {(bf16)(v[0] + bb.x), (bf16)(v[1] + bb.y), (bf16)(v[2] + bb.z), (bf16)(v[3] + bb.w)};
+    *reinterpret_cast<bf16x4 *>(smem + Q_OFF + (hh * LMAX + mq) * QP + dim * 2) = o;
+  }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  bar();
+
+  // fc weights for this wave's two column blocks, all 8 k-steps: in flight during attention
+  const rsrc_t wf = rsrc(p.wfc, (uint32_t)D * D * 2u);
+  bf16x8 fw[D / 32][2];
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int nb = 2 * w + i;
+      fw[ks][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 wf, (uint32_t)lane * 16u + (uint32_t)(nb & 3) * 1024u,
+                                                 (uint32_t)(((nb >> 2) * (D / 32) + ks) * kUnit), 0));
+    }
+  // ---- phase 2: attention, wave h < 2 = head h, queries 16 q + li (enc_attn_block_kernel's per-wave
+  // arithmetic on one 64-key tile: keys >= len at -inf; len > 0 here)
+  f32x4 oacc[DK / 16];
+  float l_run = 0.f;
+  if (w < 2) {
+    const int h = w;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      qf[s] = *reinterpret_cast<const bf16x8 *>(smem + Q_OFF + (h * LMAX + mq) * QP + (32 * s + 8 * g) * 2);
+#pragma unroll
+    for (int i = 0; i < DK / 16; ++i) oacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const char *Kb = smem + K_OFF + h * LMAX * 256;
+    const char *Vb = smem + V_OFF + h * LMAX * 256;
+    constexpr int NBK = LMAX / 16;
+    f32x4 sacc[NBK];
+#pragma unroll
+    for (int ni = 0; ni < NBK; ++ni) {
+      sacc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8 *>(Kb + kv_off(ni * 16 + li, 4 * s + g));
+        sacc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[s], sacc[ni], 0, 0, 0);
+      }
+    }
+    const int lim = len - 4 * g;  // scores of query li: keys ni*16 + 4g + j
+#pragma unroll
+    for (int ni = 0; ni < NBK; ++ni)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (ni * 16 + j >= lim) sacc[ni][j] = -INFINITY;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int ni = 0; ni < NBK; ++ni) {
+      mx = max_nn(max_nn(mx, sacc[ni][0]), sacc[ni][1]);
+      mx = max_nn(max_nn(mx, sacc[ni][2]), sacc[ni][3]);
+    }
+    const float m_new = rows_max(mx);
+    const float mc = -m_new * p.scale_log2;
+    float sx = 0.f, sy = 0.f;
+    bf16x8 pf[NBK / 2];
+#pragma unroll
+    for (int ni = 0; ni < NBK; ++ni)
+#pragma unroll
+      for (int jp = 0; jp < 2; ++jp) {
+        const float px = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[ni][2 * jp], p.scale_log2, mc));
+        const float py = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[ni][2 * jp + 1], p.scale_log2, mc));
+        sx += px;
+        sy += py;
+        pf[ni >> 1][(ni & 1) * 4 + 2 * jp] = (bf16)px;
+        pf[ni >> 1][(ni & 1) * 4 + 2 * jp + 1] = (bf16)py;
+      }
+    l_run = rows_sum(sx + sy);
+    const int tq = li >> 2, tp = li & 3;
+#pragma unroll
+    for (int s2 = 0; s2 < NBK / 2; ++s2) {
+#pragma unroll
+      for (int h4 = 0; h4 < DK / 64; ++h4) {
+        bf16x8 vf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int nd = 4 * h4 + i;
+          const char *vp = Vb + kv_off(4 * g + tq, nd * 2 + (tp >> 1)) + (tp & 1) * 8 + s2 * 32 * 256;
+          auto lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)vp);
+          auto hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vp + 16 * 256));
+          __builtin_memcpy(&vf[i], &lo, 8);
+          __builtin_memcpy(reinterpret_cast<char *>(&vf[i]) + 8, &hi, 8);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          oacc[4 * h4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[i], pf[s2], oacc[4 * h4 + i], 0, 0, 0);
+      }
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  bar();  // both attention waves hold their Q fragments: the Q region becomes o
+  if (w < 2) {
+    // O^T[d = nd*16 + 4g + j][query li] -> o[query][h*128 + d] (bf16, as the attention launch writes)
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+#pragma unroll
+    for (int nd = 0; nd < DK / 16; ++nd) {
+      const bf16x4 o = {(bf16)(oacc[nd][0] * inv), (bf16)(oacc[nd][1] * inv), (bf16)(oacc[nd][2] * inv),
+                        (bf16)(oacc[nd][3] * inv)};
+      *reinterpret_cast<bf16x4 *>(smem + Q_OFF + mq * XP + (w * DK + nd * 16 + 4 * g) * 2) = o;
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  bar();  // o complete
+
+  // ---- phase 3: fc + bfc + x, LayerNorm, row mask, on the quarter's 16 rows
+  f32x4 fa[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) fa[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) {
+    const bf16x8 of = *reinterpret_cast<const bf16x8 *>(smem + Q_OFF + mq * XP + ks * 64 + g * 16);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) fa[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[ks][i], of, fa[i], 0, 0, 0);
+  }
+  // v = fc + bfc + x; per-row partial sum over this wave's 32 columns, the 8 partials of a row
+  // combined as enc_attn_block_kernel combines them
+  float *red = reinterpret_cast<float *>(smem + RED_OFF);
+  float part;
+  {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int n = 16 * (2 * w + i) + 4 * g;
+      const float4 bb = *reinterpret_cast<const float4 *>(vfc + n);
+      const bf16x4 xv = *reinterpret_cast<const bf16x4 *>(smem + X_OFF + mq * XP + n * 2);
+      f32x4 v = fa[i];
+      v[0] = v[0] + bb.x + (float)xv[0];
+      v[1] = v[1] + bb.y + (float)xv[1];
+      v[2] = v[2] + bb.z + (float)xv[2];
+      v[3] = v[3] + bb.w + (float)xv[3];
+      fa[i] = v;
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    part = rows_sum(s);
+  }
+  auto reduce = [&](float pv, int pass) {
+    float *rb = red + pass * LMAX * 8;
+    if (g == 0) rb[mq * 8 + w] = pv;
+    bar();
+    const float4 a = *reinterpret_cast<const float4 *>(rb + mq * 8);
+    const float4 c = *reinterpret_cast<const float4 *>(rb + mq * 8 + 4);
+    return ((a.x + a.y) + (a.z + a.w)) + ((c.x + c.y) + (c.z + c.w));
+  };
+  float mean = reduce(part, 0);
+  {
+    mean *= 1.0f / D;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      f32x4 d = fa[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[j] -= mean;
+      fa[i] = d;
+      s += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+    }
+    part = rows_sum(s);
+  }
+  const float var = reduce(part, 1);  // (its barrier also retires every wave's x reads: X becomes the staging tile)
+  {
+    const float rstd = 1.0f / sqrtf(var * (1.0f / D) + p.eps);
+    const float keep = mq < len ? 1.0f : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int n = 16 * (2 * w + i) + 4 * g;
+      const float4 gg = *reinterpret_cast<const float4 *>(vg + n);
+      const float4 be = *reinterpret_cast<const float4 *>(vb + n);
+      const f32x4 d = fa[i];
+      const bf16x4 o = {(bf16)((d[0] * rstd * gg.x + be.x) * keep), (bf16)((d[1] * rstd * gg.y + be.y) * keep),
+                        (bf16)((d[2] * rstd * gg.z + be.z) * keep), (bf16)((d[3] * rstd * gg.w + be.w) * keep)};
+      *reinterpret_cast<bf16x4 *>(smem + X_OFF + mq * XP + n * 2) = o;
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  bar();
+  // whole rows (32 x 16 B each) of the quarter's positions inside [0, L): one 16-byte piece a thread
+  if (tid < nrow * 32) orow[tid] = *reinterpret_cast<const uint4 *>(smem + X_OFF + (16 * q + (tid >> 5)) * XP + (tid & 31) * 16);
+}
+
 }  // namespace
 
 static int enc_block_launch(const void *x, const int64_t *tokens, const float *emb, int vocab, const float *pe,
@@ -901,7 +1250,17 @@ static int enc_block_launch(const void *x, const int64_t *tokens, const float *e
   const bool half = !ENC_TRACE && a.ncond == 0 && ws != nullptr && B <= 1024 &&
                     (int64_t)B * 2 * 65536 + 4096 <= ws_bytes;
   const unsigned nhalf = (unsigned)(((B + 7) / 8) * 16);
-  if (half && embed)
+  // the row-split form (4 workgroups per utterance) up to kRowsMaxB utterances: no conditioning
+  // tiles, no workspace (the head-split form), no trace build.
+  // FS2_ENC_ROWS=0 keeps one workgroup per utterance (A/B and tests: read at every launch)
+  const char *erows = getenv("FS2_ENC_ROWS");
+  const bool rows = !ENC_TRACE && a.ncond == 0 && ws == nullptr && B <= kRowsMaxB && !(erows != nullptr && erows[0] == '0');
+  const unsigned nrows = (unsigned)((4 * B + 31) & ~31);
+  if (rows && embed)
+    hipLaunchKernelGGL(enc_attn_rows_kernel<true>, dim3(nrows), dim3(NT), 0, as_stream(stream), a);
+  else if (rows)
+    hipLaunchKernelGGL(enc_attn_rows_kernel<false>, dim3(nrows), dim3(NT), 0, as_stream(stream), a);
+  else if (half && embed)
     hipLaunchKernelGGL(enc_attn_half_kernel<true>, dim3(nhalf), dim3(NT), 0, as_stream(stream), a);
   else if (half)
     hipLaunchKernelGGL(enc_attn_half_kernel<false>, dim3(nhalf), dim3(NT), 0, as_stream(stream), a);

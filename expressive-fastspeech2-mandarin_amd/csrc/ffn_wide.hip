@@ -19,7 +19,9 @@
 // from the x tile and 16 MFMAs; the B fragments of one row half are shared through L1-free LDS reads
 // (32 KB of LDS reads and 8 KB of L1 weight reads per k-step per CU: half of either unit's rate).
 //
-// Launch 2 tiles 64 rows x 64 output columns (4 column quarters per row tile): K = F split over the
+// Launch 2 has two forms. The rows form (ffn_out_rows_kernel, the default while its grid stays within
+// two rounds of the chip) gives a workgroup 16 or 32 whole rows, so the LayerNorm needs no hand-off.
+// The quarter form tiles 64 rows x 64 output columns (4 column quarters per row tile): K = F split over the
 // 4 waves (every load of the workgroup -- 128 KB of w2, 128 KB of H -- issued at once: one memory
 // round trip), the 4 partials summed in wave order through LDS, + b2 + the residual; the LayerNorm
 // needs whole 256-column rows, so each quarter stores its f32 pre-norm rows (write-through) into the
@@ -341,7 +343,227 @@ __global__ __launch_bounds__(256, 2) void ffn_hidden_kernel(WideArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// launch 2: z = H . w2^T + b2 + x on 64-row x 64-column tiles, then the LayerNorm by the last of the
+// LayerNorm of row m over all 256 columns, shared by both forms of launch 2 (one summation order:
+// their outputs are bit-identical): lane (r16, hi) holds the f32 pre-norm columns 16 i + 4 hi .. + 3,
+// i = 0..15, of its row (64 values); row sums over the 4 lanes of a row. Mask, addvecs, then the bf16
+// row into the LDS staging row dst. vec: gamma | beta (f32) in LDS.
+__device__ __forceinline__ void ln_row(const WideArgs &p, f32x4 (&v)[16], int m, int hi, const char *vec, char *dst) {
+  bool masked = false;
+  int bb = 0;
+  if (p.row_pos == nullptr) {
+    bb = m / p.T;
+    masked = p.lens != nullptr && (int64_t)(m - bb * p.T) >= p.lens[bb];
+  }
+  float4 a1[16], a2[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = 16 * i + 4 * hi;
+    a1[i] = p.av1 != nullptr ? *reinterpret_cast<const float4 *>(p.av1 + (int64_t)bb * kWD + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  const float mean = s * (1.0f / 256.0f);
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    v[i] -= mean;
+    ss += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
+  }
+  ss += __shfl_xor(ss, 16, 64);
+  ss += __shfl_xor(ss, 32, 64);
+  const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + p.eps);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = 16 * i + 4 * hi;
+    a2[i] = p.av2 != nullptr ? *reinterpret_cast<const float4 *>(p.av2 + (int64_t)bb * kWD + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float *vg = reinterpret_cast<const float *>(vec), *vb = vg + kWD;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = 16 * i + 4 * hi;
+    const float4 g = *reinterpret_cast<const float4 *>(vg + n);
+    const float4 be = *reinterpret_cast<const float4 *>(vb + n);
+    float y[4] = {v[i][0] * rstd * g.x + be.x, v[i][1] * rstd * g.y + be.y, v[i][2] * rstd * g.z + be.z,
+                  v[i][3] * rstd * g.w + be.w};
+    if (masked) y[0] = y[1] = y[2] = y[3] = 0.f;
+    // addvecs after the mask, every row
+    if (p.av1 != nullptr) {
+      y[0] += a1[i].x; y[1] += a1[i].y; y[2] += a1[i].z; y[3] += a1[i].w;
+    }
+    if (p.av2 != nullptr) {
+      y[0] += a2[i].x; y[1] += a2[i].y; y[2] += a2[i].z; y[3] += a2[i].w;
+    }
+    const bf16x4 o = {(bf16)y[0], (bf16)y[1], (bf16)y[2], (bf16)y[3]};
+    *reinterpret_cast<bf16x4 *>(dst + n * 2) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launch 2, rows form: a workgroup owns 16 RB rows x ALL 256 output columns, so the LayerNorm's whole
+// rows never leave the workgroup: no f32 workspace traffic, no arrival counter, no second pass (the
+// quarter form below pays a store / drain / atomic / reload seam per 64-row tile). K = F is split
+// over the 4 waves as in the quarter form (wave w: k-steps w F/128 .. in order); a k-step is 16 w2
+// fragments (the 4 column quarters' units of that k-step) + RB fragments of the H rows, streamed
+// through a register ring RD k-steps deep (a wave's K quarter of w2 is 128 KB at F = 1024). The 4
+// partials are summed through LDS in wave order (wave w sums column quarter w), + b2 + x in the
+// quarter form's order, the f32 pre-norm rows are exchanged through LDS and wave r < RB normalises
+// row block r with the quarter form's lane mapping (ln_row): every output bit is the quarter form's.
+// Each workgroup streams all 512 KB of w2 (L2-resident, shared by every workgroup) for its 16 RB rows.
+template <int F, int RB>
+__global__ __launch_bounds__(256, 1) void ffn_out_rows_kernel(WideArgs p) {
+  constexpr int NK = F / 32;       // k-steps of 32 hidden columns
+  constexpr int KW = NK / 4;       // per wave
+  constexpr int BM = 16 * RB;      // rows per workgroup
+  constexpr int RD = 3;            // ring depth: 3 x (64 + 4 RB) registers beside the 64 RB accumulators; loads in flight fit vmcnt's 63
+  static_assert(KW >= RD && (RD - 1) * (16 + RB) <= 63, "ring");
+  constexpr int RED = 4 * 16 * RB * 64 * 16;  // 4 waves' partial tiles: [wave][J * RB + mb][lane] f32x4
+  constexpr int ZP = kWD * 4 + 64;            // f32 pre-norm row pitch (over the partials, once they are summed)
+  constexpr int ZB = BM * ZP;
+  constexpr int OP = kWD * 2 + 16;            // bf16 output staging pitch (behind the pre-norm rows)
+  constexpr int VEC = RED;                    // gamma | beta (f32, by LDS-DMA at kernel start)
+  static_assert(ZB + BM * OP <= RED, "pre-norm rows + staging fit over the partials");
+  static_assert(RED + 2048 <= 163840, "LDS");
+  __shared__ __attribute__((aligned(16))) char smem[RED + 2048];
+  Stamps st;
+  st.at();
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // consecutive row tiles on one XCD, as launch 1 wrote their H rows
+  const int L = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  if (L >= p.ntiles) return;
+  const int M = p.rows_dev != nullptr ? min(*p.rows_dev, p.M) : p.M;
+  const int m0 = L * BM;
+  if (m0 >= M) return;
+  const int hi = lane >> 4, r16 = lane & 15;
+  if (w < 2)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(w == 0 ? p.gamma : p.beta, 1024),
+                                             (__attribute__((address_space(3))) void *)(smem + VEC + w * 1024), 16,
+                                             (uint32_t)lane * 16u, 0, 0, 0);
+  // + b2 + residual operands of this lane (rows m0 + 16 mb + r16, columns 64 w + 16 jb + 4 hi .. + 3):
+  // the oldest loads, so the ring's waits cover them
+  const rsrc_t xr = make_rsrc(p.x, p.x_bytes);
+  float4 b2v[4];
+  uint2 xv[RB][4];
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb) {
+    const int n = 64 * w + 16 * jb + 4 * hi;
+    b2v[jb] = *reinterpret_cast<const float4 *>(p.b2 + n);
+#pragma unroll
+    for (int mb = 0; mb < RB; ++mb) {
+      const int m = m0 + 16 * mb + r16;
+      xv[mb][jb] = bload8(xr, m < M ? (uint32_t)m * (uint32_t)p.xs * 2u + (uint32_t)n * 2u : kOOB);
+    }
+  }
+
+  // operand ring: k-step k of this wave's K quarter into slot k % RD (the loop is fully unrolled:
+  // every slot index is static). Column block J = 4 q + jb: unit q NK + k-step, fragment jb
+  const rsrc_t wr = make_rsrc(p.w, p.w_bytes);
+  const rsrc_t hr = make_rsrc(p.h, p.h_bytes);
+  const uint32_t wb = p.w_bytes - (uint32_t)(kWD * F * 2) + (uint32_t)(w * KW * kWUnit) + (uint32_t)lane * 16u;
+  const uint32_t hrow = (uint32_t)F * 2u;
+  uint32_t hoff[RB];
+#pragma unroll
+  for (int mb = 0; mb < RB; ++mb) {
+    const int m = m0 + 16 * mb + r16;
+    hoff[mb] = m < M ? (uint32_t)m * hrow + (uint32_t)(w * KW * 64 + hi * 16) : kOOB;
+  }
+  bf16x8 wa[RD][16], hb[RD][RB];
+  auto load_at = [&](auto KI) {
+    constexpr int k = decltype(KI)::value;
+    // all loads stay ahead of the MFMAs (left alone, hipcc sinks them to their uses)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int J = 0; J < 16; ++J)
+      wa[k % RD][J] = __builtin_bit_cast(
+          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wr, wb + (uint32_t)(((J >> 2) * NK + k) * kWUnit + (J & 3) * 1024), 0, 0));
+#pragma unroll
+    for (int mb = 0; mb < RB; ++mb)  // kOOB + k * 64 stays out of range
+      hb[k % RD][mb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hr, hoff[mb] + (uint32_t)(k * 64), 0, 0));
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  wfor<RD>([&](auto I) { load_at(I); });
+  if (WIDE_TRACE) st.at();
+
+  f32x4 acc[16][RB];
+#pragma unroll
+  for (int J = 0; J < 16; ++J)
+#pragma unroll
+    for (int mb = 0; mb < RB; ++mb) acc[J][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  wfor<KW>([&](auto KI) {
+    constexpr int k = decltype(KI)::value;
+#pragma unroll
+    for (int mb = 0; mb < RB; ++mb)
+#pragma unroll
+      for (int J = 0; J < 16; ++J)
+        acc[J][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[k % RD][J], hb[k % RD][mb], acc[J][mb], 0, 0, 0);
+    if constexpr (k + RD < KW) load_at(std::integral_constant<int, k + RD>{});
+  });
+  // the 4 K-quarter partials through LDS, summed in wave order by the wave owning column quarter w
+  f32x4 *red = reinterpret_cast<f32x4 *>(smem);
+#pragma unroll
+  for (int J = 0; J < 16; ++J)
+#pragma unroll
+    for (int mb = 0; mb < RB; ++mb) red[((w * 16 + J) * RB + mb) * 64 + lane] = acc[J][mb];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LayerNorm vectors' LDS-DMA too
+  __builtin_amdgcn_s_waitcnt(kWLgkm0);
+  __builtin_amdgcn_s_barrier();
+  st.at();
+  f32x4 zv[RB][4];
+#pragma unroll
+  for (int mb = 0; mb < RB; ++mb)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      const int J = 4 * w + jb;
+      f32x4 s = red[((0 * 16 + J) * RB + mb) * 64 + lane];
+#pragma unroll
+      for (int ww = 1; ww < 4; ++ww) s += red[((ww * 16 + J) * RB + mb) * 64 + lane];
+      const bf16x4 x4 = __builtin_bit_cast(bf16x4, xv[mb][jb]);
+      s[0] = s[0] + b2v[jb].x + (float)x4[0];
+      s[1] = s[1] + b2v[jb].y + (float)x4[1];
+      s[2] = s[2] + b2v[jb].z + (float)x4[2];
+      s[3] = s[3] + b2v[jb].w + (float)x4[3];
+      zv[mb][jb] = s;
+    }
+  __builtin_amdgcn_s_waitcnt(kWLgkm0);
+  __builtin_amdgcn_s_barrier();  // every wave has read the partials: the pre-norm rows go over them
+#pragma unroll
+  for (int mb = 0; mb < RB; ++mb)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+      *reinterpret_cast<f32x4 *>(smem + (16 * mb + r16) * ZP + (64 * w + 16 * jb + 4 * hi) * 4) = zv[mb][jb];
+  __builtin_amdgcn_s_waitcnt(kWLgkm0);
+  __builtin_amdgcn_s_barrier();
+  st.at();
+  // wave w < RB: LayerNorm of rows 16 w + r16; the bf16 rows leave as whole 512-byte rows
+  if (w < RB && m0 + 16 * w + r16 < M) {
+    f32x4 v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = *reinterpret_cast<const f32x4 *>(smem + (16 * w + r16) * ZP + (16 * i + 4 * hi) * 4);
+    ln_row(p, v, m0 + 16 * w + r16, hi, smem + VEC, smem + ZB + (16 * w + r16) * OP);
+  }
+  __builtin_amdgcn_s_waitcnt(kWLgkm0);
+  __builtin_amdgcn_s_barrier();
+#pragma unroll
+  for (int i = 0; i < BM * 32 / 256; ++i) {
+    const int e = tid + 256 * i, r = e >> 5, c = e & 31;
+    if (m0 + r < M)
+      *reinterpret_cast<uint4 *>(p.out + (int64_t)(m0 + r) * p.os + c * 8) =
+          *reinterpret_cast<const uint4 *>(smem + ZB + r * OP + c * 16);
+  }
+  if (WIDE_TRACE) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    st.at();
+    st.put(p.trace, L);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launch 2, quarter form (FS2_WIDE_OUT=0, and row counts past the rows form's two rounds):
+// z = H . w2^T + b2 + x on 64-row x 64-column tiles, then the LayerNorm by the last of the
 // row tile's 4 column quarters
 template <int F>
 __global__ __launch_bounds__(256, 1) void ffn_out_kernel(WideArgs p) {
@@ -364,7 +586,6 @@ __global__ __launch_bounds__(256, 1) void ffn_out_kernel(WideArgs p) {
   const int M = p.rows_dev != nullptr ? min(*p.rows_dev, p.M) : p.M;
   const int m0 = tile * 64;
   if (m0 >= M) return;
-  const int T = p.T;
   const int hi = lane >> 4, r16 = lane & 15;
   // the LayerNorm vectors into LDS first (only the last arriver reads them, after its vmcnt(0))
   if (w < 2)
@@ -483,57 +704,7 @@ __global__ __launch_bounds__(256, 1) void ffn_out_kernel(WideArgs p) {
     for (int i = 0; i < 16; ++i)
       v[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                            zr, ((uint32_t)m * kWD + (uint32_t)(16 * i + 4 * hi)) * 4u, 0, 16));
-    bool masked = false;
-    int bb = 0;
-    if (p.row_pos == nullptr) {
-      bb = m / T;
-      masked = p.lens != nullptr && (int64_t)(m - bb * T) >= p.lens[bb];
-    }
-    float4 a1[16], a2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int n = 16 * i + 4 * hi;
-      a1[i] = p.av1 != nullptr ? *reinterpret_cast<const float4 *>(p.av1 + (int64_t)bb * kWD + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mean = s * (1.0f / 256.0f);
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      v[i] -= mean;
-      ss += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
-    }
-    ss += __shfl_xor(ss, 16, 64);
-    ss += __shfl_xor(ss, 32, 64);
-    const float rstd = 1.0f / sqrtf(ss * (1.0f / 256.0f) + p.eps);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int n = 16 * i + 4 * hi;
-      a2[i] = p.av2 != nullptr ? *reinterpret_cast<const float4 *>(p.av2 + (int64_t)bb * kWD + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float *vg = reinterpret_cast<const float *>(smem + VEC), *vb = vg + kWD;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int n = 16 * i + 4 * hi;
-      const float4 g = *reinterpret_cast<const float4 *>(vg + n);
-      const float4 be = *reinterpret_cast<const float4 *>(vb + n);
-      float y[4] = {v[i][0] * rstd * g.x + be.x, v[i][1] * rstd * g.y + be.y, v[i][2] * rstd * g.z + be.z,
-                    v[i][3] * rstd * g.w + be.w};
-      if (masked) y[0] = y[1] = y[2] = y[3] = 0.f;
-      // addvecs after the mask, every row
-      if (p.av1 != nullptr) {
-        y[0] += a1[i].x; y[1] += a1[i].y; y[2] += a1[i].z; y[3] += a1[i].w;
-      }
-      if (p.av2 != nullptr) {
-        y[0] += a2[i].x; y[1] += a2[i].y; y[2] += a2[i].z; y[3] += a2[i].w;
-      }
-      const bf16x4 o = {(bf16)y[0], (bf16)y[1], (bf16)y[2], (bf16)y[3]};
-      *reinterpret_cast<bf16x4 *>(smem + (16 * w + r16) * OP + n * 2) = o;
-    }
+    ln_row(p, v, m, hi, smem + VEC, smem + (16 * w + r16) * OP);
   }
   __builtin_amdgcn_s_waitcnt(kWLgkm0);
   __builtin_amdgcn_s_barrier();
@@ -618,6 +789,7 @@ extern "C" int fs2_ffn_wide(const fs2_ffn_desc *d, void *hidden, int64_t hidden_
   // and H stores with the other's MFMAs (free-running decoder rows: 656 workgroups); with at most one
   // workgroup per CU to launch, extra dynamic LDS keeps it at one per CU
   constexpr int kCUs = 256;
+  constexpr int kRowsRounds = 2;  // launch 2's rows form: at most this many rounds of workgroups
   // (static LDS 52 KB; + 32 KB is past half of the CU's 160 KB)
   const size_t solo = 32 * 1024;
   if (d->KS == 9)
@@ -625,9 +797,40 @@ extern "C" int fs2_ffn_wide(const fs2_ffn_desc *d, void *hidden, int64_t hidden_
   else
     hipLaunchKernelGGL((ffn_hidden_kernel<3>), dim3(n1), dim3(256), n1 <= kCUs ? solo : 0, s, p);
   FS2_CHECK_LAUNCH();
-  // launch 2: 64-row tiles x 4 column quarters
-  p.ntiles = ntiles64;
   if (WIDE_TRACE) p.trace += 4096;
+  // launch 2, rows form: 16-row tiles (RB = 1) while they fit one round of the chip (the cfg2
+  // encoder's 4,096 rows: 256 workgroups), 32-row tiles up to kRowsRounds rounds; every workgroup
+  // streams all of w2 whatever its rows, so a second round of 16-row tiles costs more than twice the
+  // rows in one (graph-timed us per fs2_ffn_wide, quarter / RB 1 / RB 2: 4,096 rows 37.9 / 35.1 /
+  // 37.4; 8,192: 64.4 / 58.1 / 54.7; 11,141: 90.0 / 84.1 / 80.1; 16,000: 117.0 / 110.3 / 99.3).
+  // FS2_WIDE_OUT=0 keeps the quarter form, FS2_WIDE_OUT_RB=1|2 forces an instance (A/B and tests:
+  // read at every launch)
+  {
+    const char *e = getenv("FS2_WIDE_OUT"), *f = getenv("FS2_WIDE_OUT_RB");
+    int rb = 0;
+    if (e == nullptr || e[0] != '0') {
+      if (f != nullptr && (f[0] == '1' || f[0] == '2'))
+        rb = f[0] - '0';
+      else
+        rb = Mg <= 16 * kCUs ? 1 : Mg <= 32 * kRowsRounds * kCUs ? 2 : 0;
+    }
+    if (rb != 0) {
+      p.ntiles = (int)((Mg + 16 * rb - 1) / (16 * rb));
+      const int nr = (p.ntiles + 7) & ~7;
+      if (d->F == 1024 && rb == 1)
+        hipLaunchKernelGGL((ffn_out_rows_kernel<1024, 1>), dim3(nr), dim3(256), 0, s, p);
+      else if (d->F == 1024)
+        hipLaunchKernelGGL((ffn_out_rows_kernel<1024, 2>), dim3(nr), dim3(256), 0, s, p);
+      else if (rb == 1)
+        hipLaunchKernelGGL((ffn_out_rows_kernel<512, 1>), dim3(nr), dim3(256), 0, s, p);
+      else
+        hipLaunchKernelGGL((ffn_out_rows_kernel<512, 2>), dim3(nr), dim3(256), 0, s, p);
+      FS2_CHECK_LAUNCH();
+      return FS2_OK;
+    }
+  }
+  // launch 2, quarter form: 64-row tiles x 4 column quarters
+  p.ntiles = ntiles64;
   const int n2 = (ntiles64 * 4 + 7) & ~7;
   if (d->F == 1024)
     hipLaunchKernelGGL((ffn_out_kernel<1024>), dim3(n2), dim3(256), 0, s, p);

@@ -718,8 +718,10 @@ def ffn_wide_ok(rows, F, ks):
 def ffn_wide(x, w_packed, b1, b2, *, ks, pad, ln, lens=None, addvec1=None, addvec2=None, layout=None, out=None):
     """fs2_ffn_wide: the FFN of :func:`ffn` (same weights, masks, addvecs, padded or packed rows) as
     two wide-tile launches for small row counts: the [rows, F] hidden goes through a bf16 buffer
-    (8 MB at the cfg2 encoder's 4k rows, L2 / MALL resident) and the LayerNorm is finished by the
-    last of 4 column-quarter workgroups per 64-row tile."""
+    (8 MB at the cfg2 encoder's 4k rows, L2 / MALL resident); the second launch gives a workgroup
+    16 or 32 whole rows (the LayerNorm stays inside it), or with FS2_WIDE_OUT=0 / past two rounds
+    of such tiles the LayerNorm is finished by the last of 4 column-quarter workgroups per 64-row
+    tile (bit-identical)."""
     _gpu(x, w_packed, b1, b2, lens, addvec1, addvec2)
     if x.dtype != torch.bfloat16 or w_packed.dtype != torch.bfloat16:
         raise TypeError("fs2amd.ffn_wide: bf16 activations and weights only")
@@ -909,8 +911,9 @@ def enc_attn_block(x, lens, wqkv_frag, bqkv, wfc_frag, bfc, ln, n_head, d_k, tem
 def _enc_ws(device):
     """(pointer, bytes) of the split-K workspace for fs2_enc_attn_block's head-split form
     (FS2_ENC_HALF=1, A/B: measured no faster than one workgroup per utterance, profiles/r5y), or
-    (None, 0): one workgroup per utterance (the default). FS2_ENC_TRACE=1 (trace builds): the
-    workspace carries the phase stamps."""
+    (None, 0): the library's own choice -- four workgroups per utterance (16 query rows each) up
+    to 64 utterances, one per utterance beyond or with FS2_ENC_ROWS=0 (bit-identical).
+    FS2_ENC_TRACE=1 (trace builds): the workspace carries the phase stamps."""
     if os.environ.get("FS2_ENC_HALF", "0") != "1" and os.environ.get("FS2_ENC_TRACE", "0") != "1":
         return None, 0
     ws = splitk_workspace(device)

@@ -3,7 +3,9 @@
 
     python tools/kernel_probe.py conv9 --reps 20
 kernels: ffn (decoder fused FFN, fs2_ffn), enc_ffn_wide / ffn_wide_rows (fs2_ffn_wide at the encoder shape /
-on --rows packed decoder rows), ffn_rows / ffn2_rows (decoder FFN fused / two launches on --rows
+on --rows packed decoder rows), enc_ffn_out (enc_ffn_wide with --time on both sides of FS2_WIDE_OUT: the
+difference is launch 2's, launch 1 is common), enc_attn (fs2_enc_attn_block at --batch x 64 with --time on both
+sides of FS2_ENC_ROWS), ffn_rows / ffn2_rows (decoder FFN fused / two launches on --rows
 packed rows), enc_ffn (encoder FFN fused, --nsplit), conv9 (decoder FFN Conv1d k=9 256->1024), conv1 (FFN k=1 1024->256 + res + LN),
 qkv, attn, lr (LengthRegulator gather + PE), lr_pad / lr_pad4 (fs2_length_regulate at cfg2 / cfg4), lr_fused / lr_proj (the forward's LR launch without / with
 the first Q|K|V), postnet (512->512 k=5 + tanh), vpf / vpf_dp / vpf_en
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--nsplit", type=int, default=None, help="ffn / enc_ffn / ffn_rows: fs2_ffn split-hidden workgroups per tile")
     ap.add_argument("--tile-rows", type=int, default=None, help="ffn / enc_ffn / ffn_rows: fs2_ffn tile rows (112 / 64)")
     ap.add_argument("--rows", type=int, default=11141, help="ffn_rows / ffn2_rows: packed decoder rows (free-running cfg2: 11141)")
+    ap.add_argument("--batch", type=int, default=64, help="enc_attn: utterances (of 64 phonemes)")
     ap.add_argument("--flush", type=int, default=0, help="MB written before each launch (cold L2 / MALL); --time subtracts it")
     a = ap.parse_args()
     import bench
@@ -47,6 +50,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     rnd = lambda *s: torch.randn(*s, generator=g).to(dev, dt)
     lens = b["mel_lens"]
+    variants = [None]  # --time: (environment variable, value) pairs to time the kernel under, in turn
     # decoder kernels run on packed valid frames, as in the forward (runtime._stage2)
     lay = ops.SeqLayout(lens, T)
     if a.kernel == "conv9" and lp.fp8 is not None:
@@ -84,10 +88,18 @@ def main():
         xe = rnd(64, 64, 256)
         fn = lambda: ops.ffn(xe, el.w12, el.b1, el.b2, ks=9, pad=4, ln=el.ln2, lens=b["src_lens"], nsplit=a.nsplit,
                               tile_rows=a.tile_rows)
-    elif a.kernel == "enc_ffn_wide":  # encoder FFN as fs2_ffn_wide (two wide-tile launches)
+    elif a.kernel in ("enc_ffn_wide", "enc_ffn_out"):  # encoder FFN as fs2_ffn_wide (two wide-tile launches)
+        if a.kernel == "enc_ffn_out":  # launch 2's forms: quarter tiles + hand-off / whole rows (read per launch)
+            variants = [("FS2_WIDE_OUT", "0"), ("FS2_WIDE_OUT", "1")]
         el = P.enc_layers[0]
         xe = rnd(64, 64, 256)
         fn = lambda: ops.ffn_wide(xe, el.w12, el.b1, el.b2, ks=9, pad=4, ln=el.ln2, lens=b["src_lens"])
+    elif a.kernel == "enc_attn":  # encoder attention sub-layer: one workgroup per utterance / four (read per launch)
+        variants = [("FS2_ENC_ROWS", "0"), ("FS2_ENC_ROWS", "1")]
+        el = P.enc_layers[0]
+        xa = rnd(a.batch, 64, 256)
+        la = torch.randint(20, 65, (a.batch,), generator=g).to(dev)
+        fn = lambda: ops.enc_attn_block(xa, la, el.wqf, el.bqkv, el.wfcf, el.bfc, el.ln1, 2, 128, 128 ** 0.5)
     elif a.kernel == "ffn_wide_rows":  # decoder FFN as fs2_ffn_wide on --rows packed rows
         l3 = torch.full((64,), a.rows // 64, dtype=torch.int64)
         l3[: a.rows - int(l3.sum())] += 1
@@ -277,7 +289,11 @@ def main():
         def fn():
             flush_buf.zero_()
             fn0()
-    if a.time:
+    for var in variants if a.time else []:
+        tag = a.kernel
+        if var is not None:
+            os.environ[var[0]] = var[1]
+            tag = f"{a.kernel} {var[0]}={var[1]}"
         # the reps are captured as one HIP graph and replayed: small launches are host-bound when
         # issued from Python one by one (~15 us of ctypes / allocator work per call)
         s = torch.cuda.Stream(dev)
@@ -313,9 +329,10 @@ def main():
                 e1.record(s)
                 e1.synchronize()
             tf = e0.elapsed_time(e1) * 1e3 / (3 * a.reps)
-            print(f"{a.kernel}: {t - tf:.2f} us/launch (graph, after a {a.flush} MB flush: {t:.2f} - {tf:.2f})")
-            return
-        print(f"{a.kernel}: {t:.2f} us/launch (graph)")
+            print(f"{tag}: {t - tf:.2f} us/launch (graph, after a {a.flush} MB flush: {t:.2f} - {tf:.2f})")
+            continue
+        print(f"{tag}: {t:.2f} us/launch (graph)")
+    if a.time:
         return
     for _ in range(a.reps):
         fn()
