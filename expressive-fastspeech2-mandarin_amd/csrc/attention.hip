@@ -690,9 +690,9 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void attn32_kernel(const bf16 *_
     voff[db][0] = kv32_off(vrow, ch) + 8 * (tp & 1);
     voff[db][1] = kv32_off(8 + vrow, ch) + 8 * (tp & 1);
   }
-  // online softmax with a lazy running max (FlashAttention-4's threshold): the running reference
-  // m_run moves (and O / l are rescaled) only when some lane's tile maximum exceeds it by more than
-  // 2^kLazy in the exponentiated domain; otherwise p = exp2((s - m_run) * scale) stays <= 2^kLazy,
+  // online softmax with a lazy running max (FlashAttention-4's threshold): a query's running
+  // reference m_run moves (and its O / l are rescaled) only when its own tile maximum exceeds it by
+  // more than 2^kLazy in the exponentiated domain; otherwise p = exp2((s - m_run) * scale) stays <= 2^kLazy,
   // well inside bf16 / f32 range. The result is the same softmax (O / l and lse are taken against
   // the same reference); the 64-element O rescale no longer runs on nearly every tile.
   constexpr float kLazy = 8.0f;
@@ -780,15 +780,20 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void attn32_kernel(const bf16 *_
       auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
       mx = max_nn(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
     }
-    // first tile: m_run = -inf, so the difference is +inf and every lane takes its maximum
-    if (__builtin_amdgcn_ballot_w64((mx - m_run) * scale_log2 > kLazy) != 0) {
-      const float alpha = __builtin_amdgcn_exp2f((m_run - mx) * scale_log2);
+    // first tile: m_run = -inf, so the difference is +inf and every lane takes its maximum. The
+    // ballot only guards the branch (wave-uniform): a lane under the threshold keeps its m_run and
+    // its alpha is exp2(0) = 1 exactly, so a query's arithmetic does not depend on the other 31
+    // queries of its wave (padded rows in one layout, zero-Q rows in the other)
+    const bool over = (mx - m_run) * scale_log2 > kLazy;
+    if (__builtin_amdgcn_ballot_w64(over) != 0) {
+      const float m_new = over ? mx : m_run;
+      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2);
       l_run *= alpha;
 #pragma unroll
       for (int i = 0; i < DK / 32; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[i][r] = __builtin_fmaf(oacc[i][r], alpha, 0.0f);
-      m_run = mx;
+      m_run = m_new;
     }
     const float mc = -m_run * scale_log2;
     float sx = 0.f, sy = 0.f;
