@@ -1,9 +1,12 @@
 """fs2amd — MI355X-native FastSpeech2 mel-synthesis forward (HIP/CDNA4 kernels behind a C ABI).
 
     from fs2amd import FastSpeech2          # drop-in for the reference model/fastspeech2.py
+    from fs2amd import TacotronSTFT         # drop-in for the reference audio/stft.py (mel / energy targets)
 """
+from .audio import TacotronSTFT, extract_features, get_mel_from_wav, mel_filterbank
 from .loss import FastSpeech2Loss
 from .model import FastSpeech2, LengthRegulator
 from .optimizer import ScheduledOptim
 
-__all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator"]
+__all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator", "TacotronSTFT",
+           "get_mel_from_wav", "extract_features", "mel_filterbank"]

@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "_lib", "libfs2hip.so")
 
 FS2_F32, FS2_BF16, FS2_FP8 = 0, 1, 2
+FS2_I16 = 3  # include/fs2hip_audio.h: int16 PCM, waveform input only
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -166,6 +167,17 @@ class VpFusedMapDesc(ctypes.Structure):
     _fields_ = [("base", VpFusedDesc), ("control_map", _p)]
 
 
+class MelDesc(ctypes.Structure):
+    """Mirror of ``fs2_mel_desc`` (include/fs2hip_audio.h)."""
+
+    _fields_ = [
+        ("wav", _p), ("wav_dtype", _i), ("max_wav_value", _f), ("wav_row_stride", _i64), ("lens", _p),
+        ("lens_host", _p), ("B", _i), ("n_max", _i), ("T_out", _i), ("n_fft", _i), ("hop", _i), ("win", _i),
+        ("n_mel", _i), ("basis", _p), ("mel_basis", _p), ("clip_val", _f), ("mel", _p), ("energy", _p), ("mag", _p),
+        ("frames_out", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "fs2_version": (ctypes.c_char_p, []),
@@ -263,6 +275,13 @@ SIGNATURES_PROSODY = {
 }
 
 
+# include/fs2hip_audio.h: waveform -> log-mel + energy, and the phoneme-level segment mean
+SIGNATURES_AUDIO = {
+    "fs2_mel_spectrogram": (_i, [ctypes.POINTER(MelDesc), _p]),
+    "fs2_segment_mean": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+}
+
+
 def header_symbols(header_path):
     """Every ``fs2_*`` function declared in include/fs2hip.h (for the export test)."""
     import re
@@ -276,7 +295,8 @@ CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "fs2hip.h")
 HEADER_PROSODY = os.path.join(os.path.dirname(HEADER), "fs2hip_prosody.h")
 # public headers beside fs2hip.h that the sources include: part of the build id
-EXTRA_HEADERS = ("fs2hip_prosody.h",)
+HEADER_AUDIO = os.path.join(os.path.dirname(HEADER), "fs2hip_audio.h")
+EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -320,7 +340,8 @@ def load():
     # FS2_LIB_ALLOW_MISSING=1 (A/B runs against an older library build only): skip entry points
     # the override library does not export; calling one of them then raises AttributeError.
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
+            list(SIGNATURES_AUDIO.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -18,6 +18,10 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   transformer/Layers.py:28) as one fs2_ffn launch (inference; weights from ops.pack_ffn_weights).
 * ``fs2::conv1d(x, w_packed, bias, cin, ks, pad, compute, epilogue, out_dtype) -> y`` — fs2_conv1d
   with a plain (bias / activation) epilogue.
+* ``fs2::mel_spectrogram(wav, lens, forward_basis, mel_basis, T_out, hop, win, max_wav_value, clip_val)
+  -> (mel, energy, frames)`` — ``TacotronSTFT.mel_spectrogram`` (audio/stft.py:130-178) over a ragged
+  batch as one fs2_mel_spectrogram launch: mel f32 [B, T_out, n_mel] channels-last, energy f32
+  [B, T_out], frames int64 [B]; ``lens`` on the device (or None: full rows), ``T_out`` a host int.
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -111,4 +115,29 @@ def _conv1d_fake(x, w_packed, bias, cin, ks, pad, compute, epilogue, out_dtype):
     return x.new_empty(B, T, w_packed.shape[0], dtype=ops.torch_dtype(out_dtype))
 
 
-OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d")
+class _StftArgs:
+    """The attributes ops.mel_spectrogram reads from an STFT object, from plain op arguments."""
+
+    def __init__(self, forward_basis, mel_basis, hop, win, max_wav_value, clip_val):
+        self.forward_basis, self.mel_basis = forward_basis, mel_basis
+        self.filter_length, self.hop_length, self.win_length = forward_basis.shape[-1], hop, win
+        self.max_wav_value, self.clip_val = max_wav_value, clip_val
+
+
+@torch.library.custom_op("fs2::mel_spectrogram", mutates_args=())
+def mel_spectrogram(wav: Tensor, lens: Optional[Tensor], forward_basis: Tensor, mel_basis: Tensor, T_out: int,
+                    hop: int, win: int, max_wav_value: float, clip_val: float) -> Tuple[Tensor, Tensor, Tensor]:
+    if T_out < 1:
+        raise ValueError("fs2::mel_spectrogram: T_out must be a positive host int")
+    return ops.mel_spectrogram(wav, lens, stft=_StftArgs(forward_basis, mel_basis, hop, win, max_wav_value, clip_val),
+                               T_out=T_out)
+
+
+@mel_spectrogram.register_fake
+def _mel_spectrogram_fake(wav, lens, forward_basis, mel_basis, T_out, hop, win, max_wav_value, clip_val):
+    B = wav.shape[0]
+    return (wav.new_empty(B, T_out, mel_basis.shape[0], dtype=torch.float32),
+            wav.new_empty(B, T_out, dtype=torch.float32), wav.new_empty(B, dtype=torch.int64))
+
+
+OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d", "mel_spectrogram")

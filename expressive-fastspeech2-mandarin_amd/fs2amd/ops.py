@@ -1704,3 +1704,99 @@ def conv_wgrad(dy, x, ks, pad, dw=None, db=None, want_db=False, accumulate=False
         if db is not None:
             _defer_add(defer, ws[S * ks * N * C:], M=N, S=S, kind=0, split=sp, accumulate=acc, outs=dbs)
     return dw, db
+
+
+def mel_frames(lens, hop=256, n_fft=1024):
+    """Frames per utterance of fs2_mel_spectrogram: 1 + lens // hop, and 0 where lens <= n_fft / 2
+    (too short to reflect-pad). Tensor or int in, the same out."""
+    if torch.is_tensor(lens):
+        return torch.where(lens > n_fft // 2, 1 + lens // hop, torch.zeros_like(lens))
+    return 1 + lens // hop if lens > n_fft // 2 else 0
+
+
+def mel_spectrogram(wav, lens=None, *, stft, T_out=None, return_mag=False, out=None):
+    """fs2_mel_spectrogram (include/fs2hip_audio.h): wav [B, n_max] f32 (clipped to [-1, 1]) or int16
+    PCM (scaled by 1 / stft.max_wav_value), unit sample stride, any row stride -> (mel f32
+    [B, T_out, n_mel] channels-last, energy f32 [B, T_out], frames int64 [B][, mag f32
+    [B, T_out, n_fft/2+1]]). Rows at or past an utterance's frame count are 0.
+
+    lens: samples per utterance; None = n_max each. A CPU tensor / list is validated on the host
+    and copied to the device; a device tensor is passed as it is (no sync: T_out is then the
+    caller's promise, frames past it are dropped). T_out None: the largest frame count, from the
+    host copy of lens, or from one device->host read of a device lens.
+    stft: an object with forward_basis f32 [2*(n_fft/2+1), 1, n_fft] (or 2-D), mel_basis f32
+    [n_mel, n_fft/2+1], filter_length, hop_length, win_length, and optionally max_wav_value and
+    clip_val (fs2amd.audio.TacotronSTFT). out: (mel, energy, frames, mag or None) buffers to write
+    into (captured graphs)."""
+    _gpu(wav)
+    if wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype not in (torch.float32, torch.int16):
+        raise ValueError("fs2amd: wav must be a [B, n_max] float32 or int16 tensor with unit sample stride")
+    B, n_max = wav.shape
+    dev = wav.device
+    n_fft, hop = int(stft.filter_length), int(stft.hop_length)
+    lens_host = None
+    if lens is None:
+        lens_dev = None
+        if T_out is None:
+            T_out = max(mel_frames(n_max, hop, n_fft), 1)
+    else:
+        lens = torch.as_tensor(lens)
+        if lens.shape != (B,):
+            raise ValueError(f"fs2amd: lens must have shape [{B}], got {tuple(lens.shape)}")
+        if lens.is_cuda:
+            lens_dev = lens.to(torch.int64).contiguous()
+            if T_out is None:
+                T_out = max(int(mel_frames(lens_dev.clamp(max=n_max), hop, n_fft).max()), 1)
+        else:
+            lens_host = lens.to(torch.int64).contiguous()
+            lens_dev = lens_host.to(dev)
+            if T_out is None:
+                T_out = max(int(mel_frames(lens_host.clamp(max=n_max), hop, n_fft).max()), 1)
+    basis = stft.forward_basis
+    basis = basis.reshape(basis.shape[0], basis.shape[-1])
+    melb = stft.mel_basis
+    _gpu(basis, melb, lens_dev)
+    if basis.dtype != torch.float32 or melb.dtype != torch.float32 or not basis.is_contiguous() \
+            or not melb.is_contiguous():
+        raise ValueError("fs2amd: forward_basis and mel_basis must be contiguous float32")
+    n_bins, n_mel = n_fft // 2 + 1, melb.shape[0]
+    if basis.shape != (2 * n_bins, n_fft) or melb.shape != (n_mel, n_bins):
+        raise ValueError(f"fs2amd: basis {tuple(basis.shape)} / mel_basis {tuple(melb.shape)} do not fit n_fft {n_fft}")
+    if out is None:
+        mel = torch.empty(B, T_out, n_mel, device=dev, dtype=torch.float32)
+        energy = torch.empty(B, T_out, device=dev, dtype=torch.float32)
+        frames = torch.empty(B, device=dev, dtype=torch.int64)
+        mag = torch.empty(B, T_out, n_bins, device=dev, dtype=torch.float32) if return_mag else None
+    else:
+        mel, energy, frames, mag = out
+    d = L.MelDesc()
+    d.wav, d.wav_dtype = wav.data_ptr(), L.FS2_I16 if wav.dtype == torch.int16 else L.FS2_F32
+    d.max_wav_value, d.wav_row_stride = float(getattr(stft, "max_wav_value", 32768.0)), wav.stride(0) if B > 1 else n_max
+    d.lens = lens_dev.data_ptr() if lens_dev is not None else None
+    d.lens_host = lens_host.data_ptr() if lens_host is not None else None
+    d.B, d.n_max, d.T_out = B, n_max, int(T_out)
+    d.n_fft, d.hop, d.win, d.n_mel = n_fft, hop, int(stft.win_length), n_mel
+    d.basis, d.mel_basis, d.clip_val = basis.data_ptr(), melb.data_ptr(), float(getattr(stft, "clip_val", 1e-5))
+    d.mel, d.energy, d.frames_out = mel.data_ptr(), energy.data_ptr(), frames.data_ptr()
+    d.mag = mag.data_ptr() if mag is not None else None
+    L.check(_lib.fs2_mel_spectrogram(ctypes.byref(d), _stream(wav)), "fs2_mel_spectrogram")
+    return (mel, energy, frames, mag) if return_mag else (mel, energy, frames)
+
+
+def segment_mean(values, dur):
+    """fs2_segment_mean: values f32 [B, T], dur integer [B, L] -> f32 [B, L], the mean of each
+    phoneme's frames (0 where the duration is 0): the phoneme-level energy / pitch averaging of
+    preprocessor/preprocessor.py:293-302 (see the header for when the reference's in-place loop
+    equals this plain mean)."""
+    _gpu(values, dur)
+    if values.dim() != 2 or dur.dim() != 2 or values.shape[0] != dur.shape[0]:
+        raise ValueError("fs2amd: segment_mean takes values [B, T] and dur [B, L]")
+    if dur.is_floating_point():
+        raise ValueError("fs2amd: segment_mean durations must be integers")
+    values = values.to(torch.float32).contiguous()
+    dur = dur.to(torch.int64).contiguous()
+    B, T = values.shape
+    Lx = dur.shape[1]
+    out = torch.empty(B, Lx, device=values.device, dtype=torch.float32)
+    L.check(_lib.fs2_segment_mean(_ptr(values), _ptr(dur), B, T, Lx, _ptr(out), _stream(values)), "fs2_segment_mean")
+    return out

@@ -9,7 +9,8 @@ sides of FS2_ENC_ROWS), ffn_rows / ffn2_rows (decoder FFN fused / two launches o
 packed rows), enc_ffn (encoder FFN fused, --nsplit), conv9 (decoder FFN Conv1d k=9 256->1024), conv1 (FFN k=1 1024->256 + res + LN),
 qkv, attn, lr (LengthRegulator gather + PE), lr_pad / lr_pad4 (fs2_length_regulate at cfg2 / cfg4), lr_fused / lr_proj (the forward's LR launch without / with
 the first Q|K|V), postnet (512->512 k=5 + tanh), vpf / vpf_dp / vpf_en
-(fs2_vp_fused sets). --flush MB writes that much before each launch (cold caches).
+(fs2_vp_fused sets), audio_mel (fs2_mel_spectrogram on 64 utterances / 24,883 frames against the reference's
+formulation in torch fp32, alternated; always timed). --flush MB writes that much before each launch (cold caches).
 """
 import argparse
 import os
@@ -21,7 +22,84 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
+def audio_mel(a):
+    """fs2_mel_spectrogram on a cfg2-like batch (64 utterances, 24,883 frames) against what a user
+    would otherwise run on the same GPU: the reference's formulation in torch fp32, F.pad(reflect)
+    -> F.conv1d(stride = hop) with the same basis -> sqrt -> matmul -> log, as one padded batch and
+    per utterance. Rounds alternate the three; the kernel's launches are graph-replayed over
+    output buffers rotated past the 256 MB MALL; the comparators are event-timed eager calls."""
+    import json
+
+    import torch.nn.functional as F
+    from fs2amd import ops
+    from fs2amd.audio import TacotronSTFT
+
+    dev = torch.device("cuda:0")
+    stft = TacotronSTFT(1024, 256, 1024, 80, 22050, 0, 8000).to(dev)
+    g = torch.Generator().manual_seed(2)
+    frames = torch.randint(128, 651, (64,), generator=g)
+    diff = 24883 - int(frames.sum())  # spread the remainder: exactly 24,883 frames
+    frames += diff // 64
+    frames[:diff % 64] += 1
+    assert int(frames.min()) >= 3 and int(frames.sum()) == 24883
+    lens = (frames - 1) * 256 + torch.randint(0, 256, (64,), generator=g)
+    n_max, T = int(lens.max()), int(frames.max())
+    wav = (torch.rand(64, n_max, generator=g) * 2 - 1).to(dev)
+    lens_d = lens.to(dev)
+    nset = 256 * (1 << 20) // (64 * T * 81 * 4) + 2
+    outs = [(torch.empty(64, T, 80, device=dev), torch.empty(64, T, device=dev),
+             torch.empty(64, device=dev, dtype=torch.int64), None) for _ in range(nset)]
+    basis, melb = stft.forward_basis, stft.mel_basis
+
+    def torch_one(x):  # x [b, n] -> (log-mel [b, 80, t], energy [b, t]), audio/stft.py:52-81,159-178
+        x = F.pad(x.clamp(-1, 1)[:, None, None, :], (512, 512, 0, 0), mode="reflect")[:, 0]
+        ft = F.conv1d(x, basis, stride=256)
+        mag = torch.sqrt(ft[:, :513] ** 2 + ft[:, 513:] ** 2)
+        return torch.log(torch.clamp(torch.matmul(melb, mag), min=1e-5)), torch.norm(mag, dim=1)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / n
+
+    s = torch.cuda.Stream(dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        for o in outs[:2]:
+            ops.mel_spectrogram(wav, lens_d, stft=stft, T_out=T, out=o)
+        torch.cuda.synchronize(dev)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=s):
+            for o in outs:
+                ops.mel_spectrogram(wav, lens_d, stft=stft, T_out=T, out=o)
+        gr.replay()
+    torch.cuda.synchronize(dev)
+    # same values as the comparator (a sanity line, not a test)
+    m_t, e_t = torch_one(wav[5:6, :int(lens[5])])
+    err = float((outs[0][0][5, :int(frames[5])] - m_t[0].t()).abs().max())
+    torch_one(wav)
+    torch.cuda.synchronize(dev)
+    flop = 24883 * (2 * 1024 * 1026 + 2 * 513 * 80)
+    for rnd in range(a.reps):
+        t_k = timed(gr.replay, 2) / nset
+        t_b = timed(lambda: torch_one(wav), 2)
+        t_u = timed(lambda: [torch_one(wav[b:b + 1, :int(lens[b])]) for b in range(64)], 1)
+        print(json.dumps({"round": rnd, "fs2_mel_spectrogram_us": round(t_k, 1), "torch_padded_batch_us": round(t_b, 1),
+                          "torch_per_utterance_us": round(t_u, 1), "frames": 24883, "padded_frames": 64 * T,
+                          "f32_mfma_floor_fraction": round(flop / 155e12 * 1e6 / t_k, 3),
+                          "max_abs_logmel_diff_vs_torch_utt5": err}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "audio_mel":
+        ap = argparse.ArgumentParser()
+        ap.add_argument("kernel")
+        ap.add_argument("--reps", type=int, default=5, help="alternated rounds")
+        return audio_mel(ap.parse_args())
     ap = argparse.ArgumentParser()
     ap.add_argument("kernel")
     ap.add_argument("--reps", type=int, default=20)
