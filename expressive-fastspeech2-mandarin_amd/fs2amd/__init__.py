@@ -3,10 +3,12 @@
     from fs2amd import FastSpeech2          # drop-in for the reference model/fastspeech2.py
     from fs2amd import TacotronSTFT         # drop-in for the reference audio/stft.py (mel / energy targets)
 """
-from .audio import TacotronSTFT, extract_features, get_mel_from_wav, mel_filterbank
+from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, griffin_lim, inv_mel_spec, mel_filterbank,
+                    mel_to_wav, window_sumsquare)
 from .loss import FastSpeech2Loss
 from .model import FastSpeech2, LengthRegulator
 from .optimizer import ScheduledOptim
 
 __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator", "TacotronSTFT",
-           "get_mel_from_wav", "extract_features", "mel_filterbank"]
+           "get_mel_from_wav", "extract_features", "mel_filterbank", "STFT", "griffin_lim", "inv_mel_spec",
+           "mel_to_wav", "window_sumsquare"]

@@ -178,6 +178,28 @@ class MelDesc(ctypes.Structure):
     ]
 
 
+class StftDesc(ctypes.Structure):
+    """Mirror of ``fs2_stft_desc`` (include/fs2hip_audio_inv.h)."""
+
+    _fields_ = [
+        ("wav", _p), ("wav_row_stride", _i64), ("lens", _p), ("lens_host", _p), ("B", _i), ("n_max", _i),
+        ("T_out", _i), ("n_fft", _i), ("hop", _i), ("win", _i), ("clip", _i), ("basis", _p), ("mag_target", _p),
+        ("mag_row_stride", _i64), ("spec", _p), ("mag", _p), ("recomb", _p), ("frames_out", _p),
+    ]
+
+
+class IstftDesc(ctypes.Structure):
+    """Mirror of ``fs2_istft_desc`` (include/fs2hip_audio_inv.h)."""
+
+    _fields_ = [
+        ("recomb", _p), ("recomb_row_stride", _i64), ("frames", _p), ("frames_host", _p), ("B", _i), ("T_in", _i),
+        ("n_out_max", _i), ("n_fft", _i), ("hop", _i), ("win", _i), ("inv_packed", _p), ("wsum_table", _p),
+        ("wav", _p), ("wav_row_stride", _i64), ("lens_out", _p),
+    ]
+
+
+ISTFT_KPAD = 1032  # FS2_ISTFT_KPAD: the 1026 recomb channels padded to 129 groups of 8
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "fs2_version": (ctypes.c_char_p, []),
@@ -282,6 +304,13 @@ SIGNATURES_AUDIO = {
 }
 
 
+# include/fs2hip_audio_inv.h: waveform -> spectrum (with the Griffin-Lim projection) and back
+SIGNATURES_AUDIO_INV = {
+    "fs2_stft": (_i, [ctypes.POINTER(StftDesc), _p]),
+    "fs2_istft": (_i, [ctypes.POINTER(IstftDesc), _p]),
+}
+
+
 def header_symbols(header_path):
     """Every ``fs2_*`` function declared in include/fs2hip.h (for the export test)."""
     import re
@@ -296,7 +325,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "fs2hip
 HEADER_PROSODY = os.path.join(os.path.dirname(HEADER), "fs2hip_prosody.h")
 # public headers beside fs2hip.h that the sources include: part of the build id
 HEADER_AUDIO = os.path.join(os.path.dirname(HEADER), "fs2hip_audio.h")
-EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h")
+HEADER_AUDIO_INV = os.path.join(os.path.dirname(HEADER), "fs2hip_audio_inv.h")
+EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -341,7 +371,7 @@ def load():
     # the override library does not export; calling one of them then raises AttributeError.
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
-            list(SIGNATURES_AUDIO.items()):
+            list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

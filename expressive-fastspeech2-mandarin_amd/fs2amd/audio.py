@@ -1,14 +1,24 @@
-"""Training-target extraction on the GPU: the reference's ``audio/`` package (audio/stft.py:130-178
-``TacotronSTFT``, audio/tools.py:8-15 ``get_mel_from_wav``) and the per-utterance feature code of
-preprocessor/preprocessor.py:267-302, over ragged batches, as one fs2_mel_spectrogram launch
-(include/fs2hip_audio.h; exact-f32 MFMA) plus one fs2_segment_mean launch.
+"""The reference's ``audio/`` package on the GPU, over ragged batches.
+
+Forward (include/fs2hip_audio.h): audio/stft.py:130-178 ``TacotronSTFT``, audio/tools.py:8-15
+``get_mel_from_wav`` and the per-utterance feature code of preprocessor/preprocessor.py:267-302, as
+one fs2_mel_spectrogram launch (exact-f32 MFMA) plus one fs2_segment_mean launch.
 
     stft = TacotronSTFT(1024, 256, 1024, 80, 22050, 0, 8000).to("cuda")
     mel, energy = get_mel_from_wav(wav_float_numpy, stft)        # [80, T], [T] numpy, as the reference
     feats = extract_features(wavs, lens, durations, stft=stft)    # a batch: what fs2amd.pipeline collates
 
-GPU only, like the vocoder: CPU tensors raise. Out of scope here: pitch (WORLD), the inverse STFT /
-Griffin-Lim, outlier removal and the normalisation statistics.
+Inverse (include/fs2hip_audio_inv.h): ``STFT.transform`` / ``inverse`` / ``forward``
+(audio/stft.py:52-127), ``window_sumsquare`` and ``griffin_lim`` (audio/audio_processing.py:7-82) and
+``inv_mel_spec`` (audio/tools.py:18-34): a mel-spectrogram to a waveform without a vocoder
+checkpoint. A Griffin-Lim iteration is one fs2_stft launch (spectrum and projection onto the target
+magnitudes) and one fs2_istft launch (overlap-add as a gather), both exact f32.
+
+    audio = inv_mel_spec(mel_80xT, None, stft, griffin_iters=60)  # float32 samples, one utterance
+    wav, lens = mel_to_wav(mel_BxTx80, mel_lens, stft)            # a ragged batch, the model's layout
+
+GPU only, like the vocoder: CPU tensors raise. Out of scope here: pitch (WORLD), outlier removal and
+the normalisation statistics.
 """
 import numpy as np
 import torch
@@ -92,8 +102,91 @@ def n_frames(n_samples, hop_length=256, filter_length=1024):
     return 1 + n_samples // hop_length if n_samples > filter_length // 2 else 0
 
 
+def stft_inverse_basis(filter_length, hop_length, win_length=None):
+    """The inverse basis of the reference's STFT.__init__ (audio/stft.py:34-47), f32
+    [2 * (filter_length/2 + 1), 1, filter_length], built as the reference builds it: the float64
+    pseudo-inverse of (filter_length / hop_length) times the stacked Fourier basis, transposed, cast
+    to f32, multiplied in f32 by the f32 window. (The closed form agrees with the pinv to 3e-16 and
+    still differs in about 1 % of the f32 bit patterns after the cast.)"""
+    win_length = filter_length if win_length is None else win_length
+    assert filter_length >= win_length
+    scale = filter_length / hop_length
+    fb = np.fft.fft(np.eye(filter_length))
+    cutoff = filter_length // 2 + 1
+    fb = np.vstack([np.real(fb[:cutoff]), np.imag(fb[:cutoff])])
+    inv = torch.from_numpy(np.linalg.pinv(scale * fb).T[:, None, :]).to(torch.float32)
+    win = np.zeros(filter_length)
+    lpad = (filter_length - win_length) // 2
+    win[lpad:lpad + win_length] = hann_periodic(win_length)
+    inv *= torch.from_numpy(win).float()
+    return inv
+
+
+def pack_inverse_basis(inverse_basis, hop_length=256):
+    """The order fs2_istft's lanes read (include/fs2hip_audio_inv.h): f32 [129, 4, hop, 2, 4] with
+    element (g, q, r, h, e) = inverse_basis[8g + 2e + h, hop * q + r]; the 1026 channels are padded
+    with zero rows to 1032."""
+    inv = inverse_basis.reshape(inverse_basis.shape[0], inverse_basis.shape[-1])
+    C, n_fft = inv.shape
+    kpad = (C + 7) // 8 * 8
+    p = torch.zeros(kpad, n_fft, dtype=torch.float32)
+    p[:C] = inv
+    p = p.reshape(kpad // 8, 4, 2, n_fft // hop_length, hop_length)  # g, e, h, q, r
+    return p.permute(0, 3, 4, 2, 1).contiguous()
+
+
+def window_sumsquare(window, n_frames, hop_length=256, win_length=1024, n_fft=1024, dtype=np.float32, norm=None):
+    """audio/audio_processing.py:7-63 (librosa 0.6): the sum-square envelope of the window at the
+    hop length, [n_fft + hop_length * (n_frames - 1)]. The accumulator has `dtype`, the addends
+    are float64 and the frames are added in ascending order, as in the reference's loop."""
+    if window != "hann" or norm is not None:
+        raise ValueError("fs2amd.audio: only the Hann window without normalisation is built")
+    win_length = n_fft if win_length is None else win_length
+    n = n_fft + hop_length * (n_frames - 1)
+    x = np.zeros(n, dtype=dtype)
+    win_sq = np.zeros(n_fft)
+    lpad = (n_fft - win_length) // 2
+    win_sq[lpad:lpad + win_length] = hann_periodic(win_length) ** 2
+    for i in range(n_frames):
+        sample = i * hop_length
+        x[sample:min(n, sample + n_fft)] += win_sq[:max(0, min(n_fft, n - sample))]
+    return x
+
+
+def wsum_edge_table(hop_length=256, win_length=1024, n_fft=1024):
+    """window_sumsquare for fs2_istft, f32 [2 ** (n_fft / hop), hop]: position hop * j + r receives
+    the frames j - q, q = 0 .. n_fft / hop - 1, that exist; row `mask` (bit q set = frame j - q
+    exists) holds the f32 accumulator after adding win_sq[hop * q + r] for the set bits in
+    ascending frame order (descending q), float64 addends, exactly as window_sumsquare's loop."""
+    nq = n_fft // hop_length
+    win_sq = np.zeros(n_fft)
+    lpad = (n_fft - win_length) // 2
+    win_sq[lpad:lpad + win_length] = hann_periodic(win_length) ** 2
+    table = np.zeros((1 << nq, hop_length), dtype=np.float32)
+    for mask in range(1 << nq):
+        for q in reversed(range(nq)):
+            if mask >> q & 1:
+                table[mask] += win_sq[hop_length * q:hop_length * (q + 1)]
+    return table
+
+
+def window_sum_from_table(table, n_frames, hop_length=256, n_fft=1024):
+    """window_sumsquare(n_frames) looked up in wsum_edge_table as the kernel does."""
+    nq = n_fft // hop_length
+    j = np.arange(n_frames - 1 + nq)
+    mask = sum(((j - q >= 0) & (j - q < n_frames)).astype(np.int64) << q for q in range(nq))
+    return table[mask].reshape(-1)
+
+
+_INVERSE_BUFFERS = ("inverse_basis", "inverse_packed", "wsum_table")
+
+
 class STFT(torch.nn.Module):
-    """The forward half of the reference's STFT module: holds ``forward_basis``."""
+    """Drop-in for audio/stft.py:15-127. ``forward_basis`` is the module's only persistent buffer;
+    ``inverse_basis`` [1026, 1, 1024] (and the two tables fs2_istft reads, ``inverse_packed`` and
+    ``wsum_table``) are non-persistent buffers built on first use (the pseudo-inverse is about a
+    second of SVD), on the device ``forward_basis`` is on. ``lens=`` / ``frames=`` make a batch
+    ragged."""
 
     def __init__(self, filter_length, hop_length, win_length, window="hann"):
         super().__init__()
@@ -101,6 +194,42 @@ class STFT(torch.nn.Module):
             raise ValueError("fs2amd.audio: only the Hann window is built")
         self.filter_length, self.hop_length, self.win_length, self.window = filter_length, hop_length, win_length, window
         self.register_buffer("forward_basis", stft_forward_basis(filter_length, win_length))
+
+    def __getattr__(self, name):
+        d = self.__dict__
+        if name in _INVERSE_BUFFERS and name not in d.get("_buffers", {}) and not d.get("_building_inverse"):
+            d["_building_inverse"] = True  # register_buffer asks hasattr(self, name)
+            dev = self.forward_basis.device
+            inv = stft_inverse_basis(self.filter_length, self.hop_length, self.win_length)
+            self.register_buffer("inverse_basis", inv.to(dev), persistent=False)
+            self.register_buffer("inverse_packed", pack_inverse_basis(inv, self.hop_length).to(dev), persistent=False)
+            self.register_buffer("wsum_table", torch.from_numpy(
+                wsum_edge_table(self.hop_length, self.win_length, self.filter_length)).to(dev), persistent=False)
+            d["_building_inverse"] = False
+        return super().__getattr__(name)
+
+    def transform(self, input_data, lens=None):
+        """(magnitude, phase), each [B, 513, T]: the kernel's spectrum, and torch.atan2 of it."""
+        from . import ops
+
+        out = ops.stft(input_data, lens, stft=self, want=("spec", "mag"))
+        cutoff = self.filter_length // 2 + 1
+        return out.mag, torch.atan2(out.spec[:, cutoff:], out.spec[:, :cutoff])
+
+    def inverse(self, magnitude, phase, frames=None):
+        """[B, 1, 256 (T - 1)] from magnitude and phase [B, 513, T]; the recombination is torch."""
+        from . import ops
+
+        recomb = torch.cat([magnitude * torch.cos(phase), magnitude * torch.sin(phase)], dim=1)
+        n_out = self.hop_length * max(magnitude.shape[-1] - 1, 0)
+        if n_out == 0:  # one frame: the reference's trim leaves no sample
+            return magnitude.new_zeros(magnitude.shape[0], 1, 0)
+        wav, _ = ops.istft(recomb, frames, stft=self, n_out_max=n_out)
+        return wav[:, None, :]
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
 
 
 class TacotronSTFT(torch.nn.Module):
@@ -195,3 +324,78 @@ def extract_features(wavs, lens, durations=None, *, stft):
         if ph is not None:
             out["energy"].append(packed[b, T * n_mel + T + 1:][:len(durations[b])].copy())
     return out
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, frames=None, generator=None):
+    """audio/audio_processing.py:66-82: magnitudes [B, 513, T] -> signal [B, 256 (T - 1)], on the GPU
+    (fs2amd.ops.griffin_lim). angles: the initial phases [B, 513, T]; None draws them on the device
+    (same distribution as the reference's np.random.rand, not its bits). frames: frames per
+    utterance of a ragged batch; samples past 256 (frames - 1) are 0. Needs at least 4 frames per
+    utterance, as the reference's reflect padding does: ValueError below that."""
+    from . import ops
+
+    wav, _ = ops.griffin_lim(magnitudes, frames, stft=stft_fn, n_iters=n_iters, angles=angles, generator=generator)
+    return wav
+
+
+def spec_from_mel(mel, _stft):
+    """audio/tools.py:19-25: mel [n_mel, T] log-mel -> [1, 513, T] linear magnitudes, exp(mel) times
+    the mel basis times 1000, on the host in the reference's arithmetic."""
+    mel = torch.stack([torch.as_tensor(mel)])
+    mel_decompress = _stft.spectral_de_normalize(mel).transpose(1, 2).data.cpu()
+    out = torch.mm(mel_decompress[0], _stft.mel_basis.cpu())
+    return out.transpose(0, 1).unsqueeze(0) * 1000
+
+
+def write_wav_f32(path, sampling_rate, audio):
+    """A mono IEEE-float WAV file, as scipy.io.wavfile.write gives for float32 samples."""
+    import struct
+
+    data = np.ascontiguousarray(audio, dtype="<f4").tobytes()
+    fmt = struct.pack("<HHIIHH", 3, 1, sampling_rate, sampling_rate * 4, 4, 32)
+    fact = struct.pack("<I", len(data) // 4)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"fact" + struct.pack("<I", 4) + fact + \
+        b"data" + struct.pack("<I", len(data)) + data
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
+def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60, angles=None):
+    """audio/tools.py:18-34: mel [n_mel, T] -> Griffin-Lim audio of its first T - 1 frames (the
+    reference drops the last one), written to out_filename as a float32 WAV at
+    _stft.sampling_rate and returned as float32 numpy samples; out_filename None only returns
+    them. Uses ``_stft.stft_fn`` (the reference's ``_stft._stft_fn`` raises AttributeError)."""
+    dev = _stft.mel_basis.device
+    if dev.type != "cuda":
+        raise RuntimeError("fs2amd: inv_mel_spec runs on the HIP kernels only (no CPU fallback)")
+    spec = spec_from_mel(mel, _stft)[:, :, :-1].contiguous().to(dev)
+    audio = griffin_lim(spec, _stft.stft_fn, griffin_iters, angles=angles)
+    audio = audio.squeeze().cpu().numpy().astype(np.float32)
+    if out_filename is not None:
+        write_wav_f32(out_filename, _stft.sampling_rate, audio)
+    return audio
+
+
+def mel_to_wav(mel, mel_lens, stft, n_iters=60, angles=None):
+    """inv_mel_spec for a ragged batch in the model's output layout: mel [B, T, n_mel] log-mel,
+    mel_lens [B] frames -> (wav f32 [B, 256 (T - 2)] on the GPU, lens int64 numpy [B] = 256 *
+    (mel_lens - 2)): every utterance gets what inv_mel_spec gives for mel[b, :mel_lens[b]].T from
+    the same initial angles ([B, 513, T - 1]). Needs mel_lens >= 5."""
+    lens = torch.as_tensor(mel_lens).to(torch.int64).cpu()
+    B, T = mel.shape[0], mel.shape[1]
+    if lens.shape != (B,) or int(lens.max()) > T:
+        raise ValueError(f"fs2amd: mel_lens must be [{B}] frame counts of at most {T}")
+    frames = lens - 1
+    if int(frames.min()) < 4:
+        raise ValueError("fs2amd: griffin_lim needs at least 4 frames per utterance (mel_lens >= 5)")
+    dev = stft.mel_basis.device
+    if dev.type != "cuda":
+        raise RuntimeError("fs2amd: mel_to_wav runs on the HIP kernels only (no CPU fallback)")
+    n_bins = stft.mel_basis.shape[1]
+    mag = torch.zeros(B, n_bins, T - 1)
+    for b in range(B):
+        mag[b, :, :frames[b]] = spec_from_mel(mel[b, :lens[b]].t(), stft)[0, :, :-1]
+    from . import ops
+
+    wav, _ = ops.griffin_lim(mag.to(dev), frames, stft=stft, n_iters=n_iters, angles=angles)
+    return wav, (stft.hop_length * (frames - 1)).numpy()

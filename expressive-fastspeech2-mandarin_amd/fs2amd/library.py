@@ -22,6 +22,12 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   -> (mel, energy, frames)`` — ``TacotronSTFT.mel_spectrogram`` (audio/stft.py:130-178) over a ragged
   batch as one fs2_mel_spectrogram launch: mel f32 [B, T_out, n_mel] channels-last, energy f32
   [B, T_out], frames int64 [B]; ``lens`` on the device (or None: full rows), ``T_out`` a host int.
+* ``fs2::stft(wav, lens, forward_basis, T_out, hop, win, clip) -> (spec, mag, frames)`` —
+  ``STFT.transform``'s convolution (audio/stft.py:52-78) over a ragged batch as one fs2_stft launch: spec
+  f32 [B, 1026, T_out] (re rows, then im rows), mag f32 [B, 513, T_out], frames int64 [B].
+* ``fs2::istft(recomb, frames, inverse_packed, wsum_table, n_out_max, hop, win) -> (wav, lens_out)`` —
+  ``STFT.inverse`` after its recombination (audio/stft.py:88-122) as one fs2_istft launch: wav f32
+  [B, n_out_max], lens_out int64 [B] = hop * max(frames - 1, 0).
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -140,4 +146,44 @@ def _mel_spectrogram_fake(wav, lens, forward_basis, mel_basis, T_out, hop, win, 
             wav.new_empty(B, T_out, dtype=torch.float32), wav.new_empty(B, dtype=torch.int64))
 
 
-OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d", "mel_spectrogram")
+class _InvArgs:
+    """The attributes ops.stft / ops.istft read from an STFT object, from plain op arguments."""
+
+    def __init__(self, n_fft, hop, win, forward_basis=None, inverse_packed=None, wsum_table=None):
+        self.filter_length, self.hop_length, self.win_length = n_fft, hop, win
+        self.forward_basis, self.inverse_packed, self.wsum_table = forward_basis, inverse_packed, wsum_table
+
+
+@torch.library.custom_op("fs2::stft", mutates_args=())
+def stft(wav: Tensor, lens: Optional[Tensor], forward_basis: Tensor, T_out: int, hop: int, win: int,
+         clip: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    if T_out < 1:
+        raise ValueError("fs2::stft: T_out must be a positive host int")
+    o = ops.stft(wav, lens, stft=_InvArgs(forward_basis.shape[-1], hop, win, forward_basis=forward_basis), T_out=T_out,
+                 clip=clip)
+    return o.spec, o.mag, o.frames
+
+
+@stft.register_fake
+def _stft_fake(wav, lens, forward_basis, T_out, hop, win, clip):
+    B, rows = wav.shape[0], forward_basis.shape[0]
+    return (wav.new_empty(B, rows, T_out, dtype=torch.float32), wav.new_empty(B, rows // 2, T_out, dtype=torch.float32),
+            wav.new_empty(B, dtype=torch.int64))
+
+
+@torch.library.custom_op("fs2::istft", mutates_args=())
+def istft(recomb: Tensor, frames: Optional[Tensor], inverse_packed: Tensor, wsum_table: Tensor, n_out_max: int,
+          hop: int, win: int) -> Tuple[Tensor, Tensor]:
+    if n_out_max < 1:
+        raise ValueError("fs2::istft: n_out_max must be a positive host int")
+    return ops.istft(recomb, frames, stft=_InvArgs(recomb.shape[1] - 2, hop, win, inverse_packed=inverse_packed,
+                                                   wsum_table=wsum_table), n_out_max=n_out_max)
+
+
+@istft.register_fake
+def _istft_fake(recomb, frames, inverse_packed, wsum_table, n_out_max, hop, win):
+    B = recomb.shape[0]
+    return recomb.new_empty(B, n_out_max, dtype=torch.float32), recomb.new_empty(B, dtype=torch.int64)
+
+
+OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d", "mel_spectrogram", "stft", "istft")

@@ -5,6 +5,7 @@ libfs2hip.so and launches on ``torch.cuda.current_stream()``. PyTorch only provi
 memory and the stream; every arithmetic op below runs in a hand-written HIP kernel. There
 is no CPU path: CPU tensors raise.
 """
+import collections
 import ctypes
 import os
 
@@ -1800,3 +1801,194 @@ def segment_mean(values, dur):
     out = torch.empty(B, Lx, device=values.device, dtype=torch.float32)
     L.check(_lib.fs2_segment_mean(_ptr(values), _ptr(dur), B, T, Lx, _ptr(out), _stream(values)), "fs2_segment_mean")
     return out
+
+
+StftOut = collections.namedtuple("StftOut", "spec mag recomb frames")
+
+
+def _lengths_arg(lens, B, dev, name):
+    """(device int64 [B] or None, host int64 [B] or None) of a lens / frames argument: a CPU tensor
+    or list is kept for the host-side validation and copied to the device; a device tensor is
+    passed as it is (no sync)."""
+    if lens is None:
+        return None, None
+    lens = torch.as_tensor(lens)
+    if lens.shape != (B,):
+        raise ValueError(f"fs2amd: {name} must have shape [{B}], got {tuple(lens.shape)}")
+    if lens.is_cuda:
+        return lens.to(torch.int64).contiguous(), None
+    host = lens.to(torch.int64).contiguous()
+    return host.to(dev), host
+
+
+def _bin_major(t, rows, name):
+    """t [B, rows, T] f32 with unit frame stride and rows a row stride apart -> its row stride."""
+    if t.dim() != 3 or t.shape[1] != rows or t.dtype != torch.float32:
+        raise ValueError(f"fs2amd: {name} must be a float32 [B, {rows}, T] tensor")
+    B, _, T = t.shape
+    rs = t.stride(1) if rows > 1 else T
+    if (T > 1 and t.stride(2) != 1) or rs < T or (B > 1 and t.stride(0) != rows * rs):
+        raise ValueError(f"fs2amd: {name} needs unit frame stride and a batch stride of {rows} rows")
+    return rs
+
+
+def stft(wav, lens=None, *, stft, T_out=None, mag_target=None, want=("spec", "mag"), clip=False, out=None):
+    """fs2_stft (include/fs2hip_audio_inv.h): STFT.transform's convolution (audio/stft.py:52-78) over
+    a ragged batch. wav [B, n_max] f32 (not clipped unless clip=True), unit sample stride, any row
+    stride -> StftOut(spec f32 [B, 1026, T_out] (re rows, then im rows), mag f32 [B, 513, T_out],
+    recomb f32 [B, 1026, T_out], frames int64 [B]); entries not asked for are None. Columns at or
+    past an utterance's frame count are 0.
+
+    want: which of "spec" / "mag" to write. mag_target f32 [B, 513, >= T_out] (any row stride):
+    also write recomb = mag_target * spec / |spec|, and (mag_target, 0) where spec is 0: the
+    projection of a Griffin-Lim step. lens / T_out: as ops.mel_spectrogram (a device lens is passed
+    as it is, T_out is then the caller's promise). stft: an object with forward_basis,
+    filter_length, hop_length, win_length (fs2amd.audio.STFT, or a TacotronSTFT for its stft_fn).
+    out: (spec, mag, recomb, frames) buffers to write into, None where not wanted."""
+    stft = getattr(stft, "stft_fn", stft)
+    _gpu(wav, mag_target)
+    if wav.dim() != 2 or wav.stride(1) != 1 or wav.dtype != torch.float32:
+        raise ValueError("fs2amd: wav must be a [B, n_max] float32 tensor with unit sample stride")
+    B, n_max = wav.shape
+    dev = wav.device
+    n_fft, hop = int(stft.filter_length), int(stft.hop_length)
+    lens_dev, lens_host = _lengths_arg(lens, B, dev, "lens")
+    if T_out is None:
+        if lens is None:
+            T_out = max(mel_frames(n_max, hop, n_fft), 1)
+        else:
+            seen = lens_host if lens_host is not None else lens_dev
+            T_out = max(int(mel_frames(seen.clamp(max=n_max), hop, n_fft).max()), 1)
+    T_out = int(T_out)
+    basis = stft.forward_basis
+    basis = basis.reshape(basis.shape[0], basis.shape[-1])
+    _gpu(basis)
+    n_bins = n_fft // 2 + 1
+    if basis.dtype != torch.float32 or not basis.is_contiguous() or basis.shape != (2 * n_bins, n_fft):
+        raise ValueError(f"fs2amd: forward_basis {tuple(basis.shape)} must be contiguous float32 [2 * (n_fft/2 + 1), n_fft]")
+    unknown = set(want) - {"spec", "mag"}
+    if unknown:
+        raise ValueError(f"fs2amd: stft want= takes 'spec' and 'mag', got {sorted(unknown)}")
+    if out is None:
+        spec = torch.empty(B, 2 * n_bins, T_out, device=dev, dtype=torch.float32) if "spec" in want else None
+        mag = torch.empty(B, n_bins, T_out, device=dev, dtype=torch.float32) if "mag" in want else None
+        recomb = torch.empty(B, 2 * n_bins, T_out, device=dev, dtype=torch.float32) if mag_target is not None else None
+        frames = torch.empty(B, device=dev, dtype=torch.int64)
+    else:
+        spec, mag, recomb, frames = out
+        for t, rows, name in ((spec, 2 * n_bins, "spec"), (mag, n_bins, "mag"), (recomb, 2 * n_bins, "recomb")):
+            if t is not None and (tuple(t.shape) != (B, rows, T_out) or not t.is_contiguous() or t.dtype != torch.float32):
+                raise ValueError(f"fs2amd: out {name} must be contiguous float32 [{B}, {rows}, {T_out}]")
+    d = L.StftDesc()
+    d.wav, d.wav_row_stride = wav.data_ptr(), wav.stride(0) if B > 1 else n_max
+    d.lens = lens_dev.data_ptr() if lens_dev is not None else None
+    d.lens_host = lens_host.data_ptr() if lens_host is not None else None
+    d.B, d.n_max, d.T_out = B, n_max, T_out
+    d.n_fft, d.hop, d.win, d.clip = n_fft, hop, int(stft.win_length), 1 if clip else 0
+    d.basis = basis.data_ptr()
+    if mag_target is not None:
+        if mag_target.shape[0] != B or mag_target.shape[-1] < T_out:
+            raise ValueError(f"fs2amd: mag_target must be [{B}, {n_bins}, >= {T_out}], got {tuple(mag_target.shape)}")
+        d.mag_target, d.mag_row_stride = mag_target.data_ptr(), _bin_major(mag_target, n_bins, "mag_target")
+    d.spec = spec.data_ptr() if spec is not None else None
+    d.mag = mag.data_ptr() if mag is not None else None
+    d.recomb = recomb.data_ptr() if recomb is not None else None
+    d.frames_out = frames.data_ptr() if frames is not None else None
+    L.check(_lib.fs2_stft(ctypes.byref(d), _stream(wav)), "fs2_stft")
+    return StftOut(spec, mag, recomb, frames)
+
+
+_stft = stft  # griffin_lim's stft= keyword shadows the function
+
+
+def istft_len(frames, hop=256):
+    """Samples of fs2_istft for an utterance of `frames` frames: hop * max(frames - 1, 0). Tensor or
+    int in, the same out."""
+    if torch.is_tensor(frames):
+        return hop * (frames - 1).clamp(min=0)
+    return hop * max(frames - 1, 0)
+
+
+def istft(recomb, frames=None, *, stft, n_out_max=None, out=None):
+    """fs2_istft (include/fs2hip_audio_inv.h): STFT.inverse's transposed convolution, window-sum
+    division, hop-ratio scaling and trim (audio/stft.py:88-122) over a ragged batch, as one gather
+    launch. recomb f32 [B, 1026, T_in] (unit frame stride, any row stride), frames: frames per
+    utterance (None = T_in each; host data is validated and copied, a device tensor is passed as
+    it is) -> (wav f32 [B, n_out_max], lens_out int64 [B] = 256 * max(frames - 1, 0)). Samples at
+    or past lens_out are 0. n_out_max None: 256 * (T_in - 1) (at least 1).
+    stft: an object with inverse_packed, wsum_table, filter_length, hop_length, win_length
+    (fs2amd.audio.STFT, or a TacotronSTFT for its stft_fn). out: (wav, lens_out) buffers."""
+    stft = getattr(stft, "stft_fn", stft)
+    _gpu(recomb)
+    n_fft, hop = int(stft.filter_length), int(stft.hop_length)
+    rs = _bin_major(recomb, n_fft + 2, "recomb")
+    B, _, T_in = recomb.shape
+    dev = recomb.device
+    frames_dev, frames_host = _lengths_arg(frames, B, dev, "frames")
+    if n_out_max is None:
+        n_out_max = max(hop * (T_in - 1), 1)
+    n_out_max = int(n_out_max)
+    inv, wtab = stft.inverse_packed, stft.wsum_table
+    _gpu(inv, wtab)
+    if inv.dtype != torch.float32 or wtab.dtype != torch.float32 or not inv.is_contiguous() or not wtab.is_contiguous() \
+            or inv.numel() != 4 * L.ISTFT_KPAD * hop or wtab.numel() != 16 * hop:
+        raise ValueError("fs2amd: inverse_packed / wsum_table must be the contiguous float32 tables of fs2amd.audio")
+    if out is None:
+        wav = torch.empty(B, n_out_max, device=dev, dtype=torch.float32)
+        lens_out = torch.empty(B, device=dev, dtype=torch.int64)
+    else:
+        wav, lens_out = out
+        if wav.dtype != torch.float32 or wav.dim() != 2 or wav.shape != (B, n_out_max) or wav.stride(1) != 1:
+            raise ValueError(f"fs2amd: out wav must be float32 [{B}, {n_out_max}] with unit sample stride")
+    d = L.IstftDesc()
+    d.recomb, d.recomb_row_stride = recomb.data_ptr(), rs
+    d.frames = frames_dev.data_ptr() if frames_dev is not None else None
+    d.frames_host = frames_host.data_ptr() if frames_host is not None else None
+    d.B, d.T_in, d.n_out_max = B, T_in, n_out_max
+    d.n_fft, d.hop, d.win = n_fft, hop, int(stft.win_length)
+    d.inv_packed, d.wsum_table = inv.data_ptr(), wtab.data_ptr()
+    d.wav, d.wav_row_stride = wav.data_ptr(), wav.stride(0) if B > 1 else n_out_max
+    d.lens_out = lens_out.data_ptr() if lens_out is not None else None
+    L.check(_lib.fs2_istft(ctypes.byref(d), _stream(recomb)), "fs2_istft")
+    return wav, lens_out
+
+
+GRIFFIN_LIM_MIN_FRAMES = 4  # the reflect padding of the next transform needs 256 (T - 1) > 512 samples
+
+
+def griffin_lim(mag, frames=None, *, stft, n_iters=30, angles=None, generator=None, out=None, workspace=None):
+    """Griffin-Lim (audio/audio_processing.py:66-82) over a ragged batch: mag f32 [B, 513, T] target
+    magnitudes (any row stride), frames per utterance (None = T each) -> (wav f32 [B, 256 (T - 1)],
+    lens_out int64 [B]). One fs2_istft from the initial angles, then per iteration one fs2_stft
+    that projects the signal's spectrum onto mag (recomb = mag * z / |z|, no atan2 / cos / sin) and
+    one fs2_istft: two launches and one [B, 1026, T] f32 workspace, no host sync in the loop.
+
+    angles f32 [B, 513, T]: the initial phases. None draws them uniformly in [0, 2 pi) on the
+    device with `generator`; that has NO bit parity with the reference's host-side
+    np.random.rand, only the same distribution. Every utterance needs at least 4 frames (the
+    reference's reflect padding raises below that): ValueError when the host can see a smaller
+    count. When frames is host data or None nothing syncs; a device tensor is passed as it is and
+    an utterance of fewer than 4 frames then comes out as zeros.
+    out: (wav, lens_out) buffers, workspace: the [B, 1026, T] buffer (captured graphs)."""
+    stft = getattr(stft, "stft_fn", stft)
+    n_bins, hop = int(stft.filter_length) // 2 + 1, int(stft.hop_length)
+    _bin_major(mag, n_bins, "mag")
+    B, _, T = mag.shape
+    seen = T if frames is None else (None if torch.as_tensor(frames).is_cuda else int(torch.as_tensor(frames).min()))
+    if seen is not None and seen < GRIFFIN_LIM_MIN_FRAMES:
+        raise ValueError(f"fs2amd: griffin_lim needs at least {GRIFFIN_LIM_MIN_FRAMES} frames per utterance, got {seen}")
+    _gpu(mag, angles)
+    frames_dev, _ = _lengths_arg(frames, B, mag.device, "frames")
+    if angles is None:
+        angles = torch.rand(mag.shape, device=mag.device, dtype=torch.float32, generator=generator) * (2 * torch.pi)
+    elif angles.shape != mag.shape:
+        raise ValueError(f"fs2amd: angles must have mag's shape {tuple(mag.shape)}, got {tuple(angles.shape)}")
+    if workspace is None:
+        workspace = torch.empty(B, 2 * n_bins, T, device=mag.device, dtype=torch.float32)
+    n_out = hop * (T - 1)
+    torch.cat([mag * torch.cos(angles), mag * torch.sin(angles)], dim=1, out=workspace)
+    wav, lens_out = istft(workspace, frames_dev, stft=stft, n_out_max=n_out, out=out)
+    for _ in range(n_iters):
+        _stft(wav, lens_out, stft=stft, T_out=T, mag_target=mag, want=(), out=(None, None, workspace, None))
+        istft(workspace, frames_dev, stft=stft, n_out_max=n_out, out=(wav, lens_out))
+    return wav, lens_out
