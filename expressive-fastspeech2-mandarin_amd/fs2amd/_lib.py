@@ -17,6 +17,8 @@ DEFAULT_LIB = os.path.join(HERE, "_lib", "libfs2hip.so")
 
 FS2_F32, FS2_BF16, FS2_FP8 = 0, 1, 2
 FS2_I16 = 3  # include/fs2hip_audio.h: int16 PCM, waveform input only
+FS2_F64 = 4  # include/fs2hip_prep.h: IEEE double, the preprocessing entry points only
+PITCH_T_MAX, PITCH_T_MAX_NOFILL, OUTLIER_LDS_BYTES = 131072, 4096, 65536  # FS2_PITCH_T_MAX, ..., of the same header
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -26,6 +28,7 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
+_d = ctypes.c_double
 
 
 class PackDesc(ctypes.Structure):
@@ -311,6 +314,16 @@ SIGNATURES_AUDIO_INV = {
 }
 
 
+# include/fs2hip_prep.h: pitch targets, outlier fence + moments, their running merge, normalisation
+SIGNATURES_PREP = {
+    "fs2_pitch_targets": (_i, [_p, _i64, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "fs2_outlier_moments": (_i, [_p, _i, _i64, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "fs2_moments_merge": (_i, [_p, _p, _p, _i, _p, _p]),
+    "fs2_normalize_minmax_ws_bytes": (_i64, [_i]),
+    "fs2_normalize_minmax": (_i, [_p, _i, _i64, _p, _i, _i, _d, _d, _p, _p, _p, _i64, _p]),
+}
+
+
 def header_symbols(header_path):
     """Every ``fs2_*`` function declared in include/fs2hip.h (for the export test)."""
     import re
@@ -326,7 +339,8 @@ HEADER_PROSODY = os.path.join(os.path.dirname(HEADER), "fs2hip_prosody.h")
 # public headers beside fs2hip.h that the sources include: part of the build id
 HEADER_AUDIO = os.path.join(os.path.dirname(HEADER), "fs2hip_audio.h")
 HEADER_AUDIO_INV = os.path.join(os.path.dirname(HEADER), "fs2hip_audio_inv.h")
-EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h")
+HEADER_PREP = os.path.join(os.path.dirname(HEADER), "fs2hip_prep.h")
+EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -371,7 +385,7 @@ def load():
     # the override library does not export; calling one of them then raises AttributeError.
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
-            list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()):
+            list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

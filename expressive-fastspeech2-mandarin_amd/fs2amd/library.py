@@ -28,6 +28,11 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
 * ``fs2::istft(recomb, frames, inverse_packed, wsum_table, n_out_max, hop, win) -> (wav, lens_out)`` —
   ``STFT.inverse`` after its recombination (audio/stft.py:88-122) as one fs2_istft launch: wav f32
   [B, n_out_max], lens_out int64 [B] = hop * max(frames - 1, 0).
+* ``fs2::pitch_targets(f0, dur, frames) -> (out, filled, voiced)``, ``fs2::outlier_moments(values, lens)
+  -> (quartiles, inlier, count, mean, m2)``, ``fs2::moments_merge(state, count, mean, m2)`` (mutates
+  ``state``) and ``fs2::normalize_minmax(values, lens, mean, std) -> (out, minmax)`` — the corpus
+  preprocessing of preprocessor/preprocessor.py:263-291, :367-375, :152-155 and :377-388
+  (include/fs2hip_prep.h), float64 results.
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -186,4 +191,52 @@ def _istft_fake(recomb, frames, inverse_packed, wsum_table, n_out_max, hop, win)
     return recomb.new_empty(B, n_out_max, dtype=torch.float32), recomb.new_empty(B, dtype=torch.int64)
 
 
+@torch.library.custom_op("fs2::pitch_targets", mutates_args=())
+def pitch_targets(f0: Tensor, dur: Tensor, frames: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    o = ops.pitch_targets(f0, dur, frames)
+    return o.out, o.filled, o.voiced
+
+
+@pitch_targets.register_fake
+def _pitch_targets_fake(f0, dur, frames):
+    B, T = f0.shape
+    return (f0.new_empty(B, dur.shape[1], dtype=torch.float64), f0.new_empty(B, T, dtype=torch.float64),
+            f0.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("fs2::outlier_moments", mutates_args=())
+def outlier_moments(values: Tensor, lens: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return tuple(ops.outlier_moments(values, lens))
+
+
+@outlier_moments.register_fake
+def _outlier_moments_fake(values, lens):
+    B, n_max = values.shape
+    return (values.new_empty(B, 2), values.new_empty(B, n_max, dtype=torch.bool),
+            values.new_empty(B, dtype=torch.int64), values.new_empty(B, dtype=torch.float64),
+            values.new_empty(B, dtype=torch.float64))
+
+
+@torch.library.custom_op("fs2::moments_merge", mutates_args=("state",))
+def moments_merge(state: Tensor, count: Tensor, mean: Tensor, m2: Tensor) -> None:
+    ops.moments_merge(state, count, mean, m2)
+
+
+@moments_merge.register_fake
+def _moments_merge_fake(state, count, mean, m2):
+    return None
+
+
+@torch.library.custom_op("fs2::normalize_minmax", mutates_args=())
+def normalize_minmax(values: Tensor, lens: Optional[Tensor], mean: float, std: float) -> Tuple[Tensor, Tensor]:
+    return ops.normalize_minmax(values, lens, mean=mean, std=std)
+
+
+@normalize_minmax.register_fake
+def _normalize_minmax_fake(values, lens, mean, std):
+    return values.new_empty(values.shape, dtype=torch.float64), values.new_empty(2, dtype=torch.float64)
+
+
 OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d", "mel_spectrogram", "stft", "istft")
+# the corpus preprocessing ops (include/fs2hip_prep.h), listed on their own: OPS is the model's and the audio path's
+OPS_PREP = ("pitch_targets", "outlier_moments", "moments_merge", "normalize_minmax")

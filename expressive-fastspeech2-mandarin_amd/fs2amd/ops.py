@@ -1992,3 +1992,122 @@ def griffin_lim(mag, frames=None, *, stft, n_iters=30, angles=None, generator=No
         _stft(wav, lens_out, stft=stft, T_out=T, mag_target=mag, want=(), out=(None, None, workspace, None))
         istft(workspace, frames_dev, stft=stft, n_out_max=n_out, out=(wav, lens_out))
     return wav, lens_out
+
+
+PitchOut = collections.namedtuple("PitchOut", "out filled voiced")
+OutlierOut = collections.namedtuple("OutlierOut", "quartiles inlier count mean m2")
+
+
+def _ragged_rows(values, lens, name):
+    """(row stride, element code, device lens or None) of a ragged [B, n_max] f32 / f64 batch."""
+    _gpu(values)
+    if values.dim() != 2 or values.dtype not in (torch.float32, torch.float64) or values.shape[1] < 1 \
+            or values.stride(1) != 1:
+        raise ValueError(f"fs2amd: {name} must be a float32 or float64 [B, n_max >= 1] tensor with unit element stride")
+    B, n_max = values.shape
+    lens_dev, _ = _lengths_arg(lens, B, values.device, "lens")
+    _gpu(lens_dev)
+    stride = values.stride(0) if B > 1 else n_max
+    if stride < n_max:
+        raise ValueError(f"fs2amd: {name} rows overlap (row stride {stride} < {n_max})")
+    return stride, L.FS2_F64 if values.dtype == torch.float64 else L.FS2_F32, lens_dev
+
+
+def pitch_targets(f0, dur, frames=None, *, want_filled=True, out=None):
+    """fs2_pitch_targets (include/fs2hip_prep.h): f0 f64 [B, T] (0 = unvoiced; unit frame stride, any
+    row stride), dur integer [B, L] (0-padded), frames: None (T each) or [B] -> PitchOut(out f64
+    [B, L] phoneme-level means of the interpolated contour, filled f64 [B, T] the interpolated
+    contour (None unless want_filled), voiced int32 [B]). The crop is n = min(frames, T, sum(dur));
+    an utterance with voiced <= 1 is the one the reference drops: its rows are 0.
+    out: (out, filled or None, voiced) buffers to write into."""
+    _gpu(f0, dur)
+    if f0.dim() != 2 or f0.dtype != torch.float64 or f0.shape[1] < 1 or f0.stride(1) != 1:
+        raise ValueError("fs2amd: f0 must be a float64 [B, T >= 1] tensor with unit frame stride")
+    if dur.dim() != 2 or dur.shape[0] != f0.shape[0] or dur.shape[1] < 1 or dur.is_floating_point():
+        raise ValueError("fs2amd: pitch_targets takes f0 [B, T] and integer dur [B, L >= 1]")
+    B, T = f0.shape
+    if T > L.PITCH_T_MAX or (not want_filled and T > L.PITCH_T_MAX_NOFILL):
+        raise ValueError(f"fs2amd: pitch_targets covers T <= {L.PITCH_T_MAX} ({L.PITCH_T_MAX_NOFILL} without filled)")
+    stride = f0.stride(0) if B > 1 else T
+    if stride < T:
+        raise ValueError(f"fs2amd: f0 rows overlap (row stride {stride} < {T})")
+    dur = dur.to(torch.int64).contiguous()
+    Lx = dur.shape[1]
+    frames_dev, _ = _lengths_arg(frames, B, f0.device, "frames")
+    _gpu(frames_dev)
+    if out is None:
+        o = torch.empty(B, Lx, device=f0.device, dtype=torch.float64)
+        filled = torch.empty(B, T, device=f0.device, dtype=torch.float64) if want_filled else None
+        voiced = torch.empty(B, device=f0.device, dtype=torch.int32)
+    else:
+        o, filled, voiced = out
+    L.check(_lib.fs2_pitch_targets(_ptr(f0), stride, _ptr(frames_dev), _ptr(dur), B, T, Lx, _ptr(o), _ptr(filled),
+                                   _ptr(voiced), _stream(f0)), "fs2_pitch_targets")
+    return PitchOut(o, filled, voiced)
+
+
+def outlier_moments(values, lens=None, *, out=None):
+    """fs2_outlier_moments: values f32 or f64 [B, n_max] (ragged through lens [B]) -> OutlierOut(
+    quartiles [B, 2] in values' dtype (numpy's linear p25 / p75), inlier bool [B, n_max] (strictly
+    inside p25 - 1.5 iqr .. p75 + 1.5 iqr; False past lens), count int64 [B], mean f64 [B], m2 f64
+    [B] (sum of squared deviations of the inliers)): preprocessor.py:367-375 with the moments a
+    StandardScaler.partial_fit of the inliers would add. out: the five buffers to write into."""
+    stride, code, lens_dev = _ragged_rows(values, lens, "values")
+    B, n_max = values.shape
+    if n_max * values.element_size() > L.OUTLIER_LDS_BYTES:
+        raise ValueError(f"fs2amd: outlier_moments sorts at most {L.OUTLIER_LDS_BYTES // values.element_size()} "
+                         f"{values.dtype} values per utterance, got {n_max}")
+    dev = values.device
+    if out is None:
+        q = torch.empty(B, 2, device=dev, dtype=values.dtype)
+        inl = torch.empty(B, n_max, device=dev, dtype=torch.bool)
+        cnt = torch.empty(B, device=dev, dtype=torch.int64)
+        mean = torch.empty(B, device=dev, dtype=torch.float64)
+        m2 = torch.empty(B, device=dev, dtype=torch.float64)
+    else:
+        q, inl, cnt, mean, m2 = out
+    L.check(_lib.fs2_outlier_moments(_ptr(values), code, stride, _ptr(lens_dev), B, n_max, _ptr(q), _ptr(inl), _ptr(cnt),
+                                     _ptr(mean), _ptr(m2), _stream(values)), "fs2_outlier_moments")
+    return OutlierOut(q, inl, cnt, mean, m2)
+
+
+def moments_merge(state, count, mean, m2):
+    """fs2_moments_merge: folds the partials count int64 [B], mean f64 [B], m2 f64 [B] into state f64
+    [3] = (count, mean, m2) in place, in index order (Chan's update; empty partials are skipped).
+    A new state is torch.zeros(3, dtype=torch.float64) on the device. Returns state."""
+    _gpu(state, count, mean, m2)
+    if state.shape != (3,) or state.dtype != torch.float64 or not state.is_contiguous():
+        raise ValueError("fs2amd: the moments state is a contiguous float64 [3] tensor")
+    B = count.shape[0]
+    if count.dim() != 1 or B < 1 or mean.shape != (B,) or m2.shape != (B,) or count.dtype != torch.int64 \
+            or mean.dtype != torch.float64 or m2.dtype != torch.float64:
+        raise ValueError("fs2amd: moments_merge takes count int64 [B], mean float64 [B], m2 float64 [B]")
+    count, mean, m2 = count.contiguous(), mean.contiguous(), m2.contiguous()
+    L.check(_lib.fs2_moments_merge(_ptr(count), _ptr(mean), _ptr(m2), B, _ptr(state), _stream(state)),
+            "fs2_moments_merge")
+    return state
+
+
+def normalize_minmax(values, lens=None, *, mean, std, out=None, workspace=None):
+    """fs2_normalize_minmax: values f32 or f64 [B, n_max] (ragged through lens [B]), host floats mean
+    and std -> (out f64 [B, n_max] = (double(v) - mean) / std, 0 past lens; minmax f64 [2] over every
+    valid entry): preprocessor.py:377-388. out: (out, minmax) buffers; workspace: a byte tensor of
+    at least fs2_normalize_minmax_ws_bytes(B)."""
+    stride, code, lens_dev = _ragged_rows(values, lens, "values")
+    B, n_max = values.shape
+    dev = values.device
+    need = int(_lib.fs2_normalize_minmax_ws_bytes(B))
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _gpu(workspace)
+    if workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise ValueError(f"fs2amd: normalize_minmax needs a contiguous workspace of {need} bytes")
+    if out is None:
+        o = torch.empty(B, n_max, device=dev, dtype=torch.float64)
+        mm = torch.empty(2, device=dev, dtype=torch.float64)
+    else:
+        o, mm = out
+    L.check(_lib.fs2_normalize_minmax(_ptr(values), code, stride, _ptr(lens_dev), B, n_max, float(mean), float(std),
+                                      _ptr(o), _ptr(mm), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                      _stream(values)), "fs2_normalize_minmax")
+    return o, mm

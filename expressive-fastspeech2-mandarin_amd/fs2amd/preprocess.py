@@ -1,0 +1,260 @@
+"""From waveforms, F0 contours and phone alignments to a trainable corpus directory: what the
+reference's preprocessor/preprocessor.py does between feature extraction and ``stats.json``.
+
+* ``get_alignment`` — :327-365 over ``(start, end, label)`` intervals (host code).
+* ``pitch_targets`` — :263-291: crop, interpolate over unvoiced frames, phoneme mean.
+* ``remove_outlier`` / ``CorpusStats`` — :367-375 and the ``StandardScaler.partial_fit`` calls of
+  :152-155: the IQR fence per utterance and a running mean / variance kept on the device.
+* ``normalize`` — :377-388 with the switches of :161-173.
+* ``build_corpus`` — the directory layout of :183-222 and :304-325.
+
+The arithmetic runs in the kernels of include/fs2hip_prep.h (float64, uncontracted; see the header
+for what is exact). F0 estimation is not here: the contour per utterance is an input, float64, 0
+where unvoiced, as ``pyworld.stonemask`` returns it. TextGrid files are not read either.
+"""
+import json
+import os
+import random
+
+import numpy as np
+import torch
+
+SIL_PHONES = ("sil", "sp", "spn")
+
+
+def get_alignment(intervals, sampling_rate, hop_length):
+    """preprocessor.py:327-365. intervals: (start_time, end_time, label) in tier order. Returns
+    (phones, durations, start_time, end_time): leading silences dropped, trailing ones cut off,
+    inner ones kept; durations in frames. An all-silence tier gives ([], [], 0, 0): the caller drops
+    an utterance with start >= end."""
+    phones, durations = [], []
+    start_time, end_time, end_idx = 0, 0, 0
+    for s, e, p in intervals:
+        if not phones:
+            if p in SIL_PHONES:
+                continue
+            start_time = s
+        phones.append(p)
+        if p not in SIL_PHONES:
+            end_time = e
+            end_idx = len(phones)
+        durations.append(int(np.round(e * sampling_rate / hop_length) - np.round(s * sampling_rate / hop_length)))
+    return phones[:end_idx], durations[:end_idx], start_time, end_time
+
+
+def _device(device):
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise RuntimeError("fs2amd: preprocessing runs on the HIP kernels only (no CPU fallback)")
+    return dev
+
+
+def _pack(arrays, dtype):
+    """A list of 1-D arrays -> (host [B, n_max >= 1] zero-padded, int64 lens [B])."""
+    lens = np.array([len(a) for a in arrays], dtype=np.int64)
+    out = np.zeros((len(arrays), max(int(lens.max(initial=0)), 1)), dtype=dtype)
+    for b, a in enumerate(arrays):
+        out[b, :len(a)] = a
+    return out, lens
+
+
+def _common_dtype(arrays):
+    """float32 when every array is float32, else float64 (what numpy would promote to)."""
+    arrays = [np.asarray(a) for a in arrays]
+    if any(a.ndim != 1 for a in arrays):
+        raise ValueError("fs2amd: value tracks are 1-D arrays")
+    return arrays, (np.float32 if arrays and all(a.dtype == np.float32 for a in arrays) else np.float64)
+
+
+def pitch_targets(f0_list, durations, *, device=None, return_filled=False):
+    """Phoneme-level pitch targets of a batch: f0_list float64 contours (0 = unvoiced), durations
+    integer arrays (frames per phoneme). Returns a list with a float64 [L_b] array per utterance, or
+    None where the reference drops it (at most one voiced frame within sum(duration)).
+    return_filled: also the interpolated frame-level contours [min(len(f0), sum(d))] (None likewise)."""
+    from . import ops
+
+    dev = _device(device)
+    if len(f0_list) != len(durations):
+        raise ValueError("fs2amd: one duration array per contour")
+    f0, frames = _pack([np.asarray(f, dtype=np.float64) for f in f0_list], np.float64)
+    dur, n_ph = _pack([np.asarray(d, dtype=np.int64) for d in durations], np.int64)
+    o = ops.pitch_targets(torch.from_numpy(f0).to(dev), torch.from_numpy(dur).to(dev), torch.from_numpy(frames))
+    out, filled, voiced = o.out.cpu().numpy(), o.filled.cpu().numpy(), o.voiced.cpu().numpy()
+    res, fil = [], []
+    for b in range(len(f0_list)):
+        keep = voiced[b] > 1
+        n = min(int(frames[b]), int(np.maximum(dur[b], 0).sum()))
+        res.append(out[b, :n_ph[b]].copy() if keep else None)
+        fil.append(filled[b, :n].copy() if keep else None)
+    return (res, fil) if return_filled else res
+
+
+def _fence(arrays, dev):
+    """ops.outlier_moments over a list of tracks: (OutlierOut, host lens, packed device values)."""
+    from . import ops
+
+    arrays, dtype = _common_dtype(arrays)
+    vals, lens = _pack(arrays, dtype)
+    v = torch.from_numpy(vals).to(dev)
+    return ops.outlier_moments(v, torch.from_numpy(lens)), lens, arrays
+
+
+def remove_outlier(values, *, device=None):
+    """preprocessor.py:367-375: the values strictly inside [p25 - 1.5 iqr, p75 + 1.5 iqr], in order,
+    in the input's dtype (float32 stays float32; anything else is taken as float64)."""
+    o, lens, arrays = _fence([values], _device(device))
+    return arrays[0][o.inlier[0, :lens[0]].cpu().numpy()]
+
+
+class CorpusStats:
+    """The running mean and variance of the reference's StandardScaler over outlier-free values
+    (preprocessor.py:125-126, :152-155), kept on the device: ``partial_fit`` makes no device-to-host
+    copy; the attributes read the three-number state when asked."""
+
+    def __init__(self, device=None):
+        self.device = _device(device)
+        self.state = torch.zeros(3, dtype=torch.float64, device=self.device)
+
+    def partial_fit(self, arrays):
+        """The IQR fence of every array, the moments of its inliers, and their merge into the state,
+        in list order; an array without inliers (or an empty list) leaves the state as it is."""
+        from . import ops
+
+        if len(arrays) == 0:
+            return self
+        o, _, _ = _fence(arrays, self.device)
+        ops.moments_merge(self.state, o.count, o.mean, o.m2)
+        return self
+
+    def _host(self):
+        n, mean, m2 = self.state.cpu().tolist()
+        return n, mean, m2
+
+    @property
+    def n_samples_seen_(self):
+        return int(self._host()[0])
+
+    @property
+    def mean_(self):
+        return self._host()[1]
+
+    @property
+    def var_(self):
+        n, _, m2 = self._host()
+        return m2 / n if n > 0 else 0.0
+
+    @property
+    def scale_(self):
+        """sqrt(var_), and 1.0 where the variance is 0, as sklearn's _handle_zeros_in_scale."""
+        var = self.var_
+        return float(np.sqrt(var)) if var > 0.0 else 1.0
+
+
+def normalize(arrays, mean, std, *, device=None):
+    """preprocessor.py:377-388 over a list of tracks: ((v - mean) / std per track as float64, min,
+    max) with min / max over every value, outliers included. With mean = 0 and std = 1 (the
+    reference's way of switching normalisation off) the arrays come back as they are, in their own
+    dtype, as ``(values - 0) / 1`` leaves them."""
+    from . import ops
+
+    arrays, dtype = _common_dtype(arrays)
+    if not arrays:
+        return [], float(np.finfo(np.float64).max), float(np.finfo(np.float64).min)
+    vals, lens = _pack(arrays, dtype)
+    out, mm = ops.normalize_minmax(torch.from_numpy(vals).to(_device(device)), torch.from_numpy(lens), mean=mean, std=std)
+    vmin, vmax = mm.cpu().tolist()
+    if mean == 0 and std == 1:
+        return [a.copy() for a in arrays], vmin, vmax
+    out = out.cpu().numpy()
+    return [out[b, :lens[b]].copy() for b in range(len(arrays))], vmin, vmax
+
+
+def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None, seed=1234, batch_size=16,
+                 emotions=None):
+    """Write a preprocessed corpus directory (preprocessor.py:116-224, :304-325) from utterances, an
+    iterable of dicts with ``basename``, ``speaker``, ``phones`` (list of labels), ``raw_text``,
+    ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
+    int16), ``f0`` (float64 contour at the STFT's hop, 0 = unvoiced) and ``durations`` (frames per
+    phoneme). stft: a fs2amd.audio.TacotronSTFT on the GPU. val_size: None = the configuration's.
+
+    Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
+    batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
+    energy are phoneme-level or frame-level and normalised or not as
+    preprocess_config["preprocessing"] says. Written: duration/ (int64), pitch/ (float64), energy/
+    (float64 when normalised, else float32), mel/ ([T, n_mel] float32) as <speaker>-<kind>-<basename>.npy,
+    stats.json ([min, max, mean, std] for pitch and energy), speakers.json (speaker -> index in
+    order of first appearance), emotions.json when ``emotions`` is given, and train.txt / val.txt:
+    the lines shuffled by random.Random(seed), the first val_size to val.txt. Returns the lines."""
+    from .audio import extract_features
+
+    pp = preprocess_config["preprocessing"]
+    dev = stft.mel_basis.device
+    if val_size is None:
+        val_size = pp["val_size"]
+    ph_pitch, ph_energy = pp["pitch"]["feature"] == "phoneme_level", pp["energy"]["feature"] == "phoneme_level"
+    for feat in (pp["pitch"]["feature"], pp["energy"]["feature"]):
+        if feat not in ("phoneme_level", "frame_level"):
+            raise ValueError(f"fs2amd: unknown feature level {feat!r}")
+    for kind in ("mel", "pitch", "energy", "duration"):
+        os.makedirs(os.path.join(out_dir, kind), exist_ok=True)
+    pitch_stats, energy_stats = CorpusStats(dev), CorpusStats(dev)
+    speakers, lines, kept = {}, [], []  # kept: (speaker, basename, pitch, energy)
+
+    def flush(batch):
+        wavs = [np.asarray(u["wav"]) for u in batch]
+        wdtype = np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32
+        wav, lens = _pack(wavs, wdtype)
+        durs = [np.asarray(u["durations"], dtype=np.int64) for u in batch]
+        feats = extract_features(torch.from_numpy(wav).to(dev), lens, durs, stft=stft)
+        f0s = [np.asarray(u["f0"], dtype=np.float64) for u in batch]
+        ph = pitch_targets(f0s, durs, device=dev)
+        pitches, energies = [], []
+        for b, u in enumerate(batch):
+            if ph[b] is None:  # preprocessor.py:264-265
+                continue
+            spk, name = u["speaker"], u["basename"]
+            speakers.setdefault(spk, len(speakers))
+            # frame level: the cropped contour as it is (the reference interpolates only before averaging)
+            pitch = ph[b] if ph_pitch else f0s[b][:max(int(durs[b].sum()), 0)]
+            energy = feats["energy"][b] if ph_energy else feats["energy_frame"][b]
+            np.save(os.path.join(out_dir, "duration", f"{spk}-duration-{name}.npy"), durs[b])
+            np.save(os.path.join(out_dir, "mel", f"{spk}-mel-{name}.npy"), feats["mel"][b])
+            kept.append((spk, name, pitch, energy))
+            pitches.append(pitch)
+            energies.append(energy)
+            lines.append("|".join([name, spk, "{" + " ".join(u["phones"]) + "}", u["raw_text"], u["aux"]]))
+        pitch_stats.partial_fit(pitches)
+        energy_stats.partial_fit(energies)
+
+    batch = []
+    for u in utterances:
+        batch.append(u)
+        if len(batch) == batch_size:
+            flush(batch)
+            batch = []
+    if batch:
+        flush(batch)
+
+    p_mean, p_std = (pitch_stats.mean_, pitch_stats.scale_) if pp["pitch"]["normalization"] else (0, 1)
+    e_mean, e_std = (energy_stats.mean_, energy_stats.scale_) if pp["energy"]["normalization"] else (0, 1)
+    stats = {}
+    for kind, idx, mean, std in (("pitch", 2, p_mean, p_std), ("energy", 3, e_mean, e_std)):
+        values, vmin, vmax = normalize([k[idx] for k in kept], mean, std, device=dev)
+        for k, v in zip(kept, values):
+            np.save(os.path.join(out_dir, kind, f"{k[0]}-{kind}-{k[1]}.npy"), v)
+        stats[kind] = [float(vmin), float(vmax), float(mean), float(std)]
+    with open(os.path.join(out_dir, "speakers.json"), "w") as f:
+        f.write(json.dumps(speakers))
+    if emotions:
+        with open(os.path.join(out_dir, "emotions.json"), "w") as f:
+            f.write(json.dumps(emotions))
+    with open(os.path.join(out_dir, "stats.json"), "w") as f:
+        f.write(json.dumps(stats))
+    random.Random(seed).shuffle(lines)
+    with open(os.path.join(out_dir, "train.txt"), "w", encoding="utf-8") as f:
+        for m in lines[val_size:]:
+            f.write(m + "\n")
+    with open(os.path.join(out_dir, "val.txt"), "w", encoding="utf-8") as f:
+        for m in lines[:val_size]:
+            f.write(m + "\n")
+    return lines
