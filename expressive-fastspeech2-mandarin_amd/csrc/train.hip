@@ -1316,7 +1316,8 @@ extern "C" int fs2_loss_bwd(const fs2_loss_args *a, const float *grad_out, const
 // PostNet layer in train mode (transformer/Layers.py:92-137, training.py): BatchNorm1d on batch
 // statistics over all B*T frames (running stats updated with momentum, unbiased variance), tanh
 // (layers 0..3), F.dropout(0.5). Statistics: per block a two-pass (mean, M2) over its row chunk,
-// combined in block order with Chan's formula (deterministic, no E[z^2] - E[z]^2 cancellation).
+// combined in block order in double with Chan's formula (deterministic, no E[z^2] - E[z]^2
+// cancellation, no row that the sums are shifted by).
 // The backward recomputes zhat and tanh from z and regenerates the dropout bits.
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -1352,23 +1353,42 @@ __device__ __forceinline__ void bn_row_reduce(float *red, const BnGeom &g, int C
       for (int q = 0; q < 4; ++q) v[q] += red[r * C + g.cg * 4 + q];
 }
 
-// part[blk][c][2] = (sum (z - K_c), sum (z - K_c)^2) over the block's rows, K_c = z[0][c]: shifted
-// sums (no E[z^2] - E[z]^2 cancellation for |mean| >> std), added in a fixed order by the finish
+// part[blk][c][3] = (m, sum (z - m), sum (z - m)^2) over the block's rows, m = the f32 mean of those
+// rows from a first pass over the chunk (the second pass reads it again from L2). The deviations are
+// taken about the block's own mean, so no row (not row 0 either) is special; sum (z - m) keeps what
+// the f32 mean lost to rounding. An empty block (r0 >= R) writes zeros.
 __global__ __launch_bounds__(256) void bn_stats_part_kernel(const float *__restrict__ z, int64_t R, int C, int rpb,
                                                             float *__restrict__ part) {
   extern __shared__ float red[];
   const BnGeom g = bn_geom(C);
   const int64_t r0 = (int64_t)blockIdx.x * rpb, r1 = r0 + rpb < R ? r0 + rpb : R;
+  const float inv = r1 > r0 ? 1.0f / (float)(r1 - r0) : 0.0f;
+  float m[4] = {0.f, 0.f, 0.f, 0.f};
+  if (g.active)
+#pragma unroll 4
+    for (int64_t r = r0 + g.rsub; r < r1; r += g.RPI) {
+      float v[4];
+      load4(z + r * C + g.cg * 4, v);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) m[q] += v[q];
+    }
+  bn_row_reduce(red, g, C, m);
+  __syncthreads();  // every row slot's sum has been read: red[0 .. C) now carries the block mean
+  if (g.active && g.rsub == 0)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[g.cg * 4 + q] = m[q] * inv;
+  __syncthreads();
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   if (g.active) {
-    float K[4];
-    load4(z + g.cg * 4, K);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) m[q] = red[g.cg * 4 + q];
+#pragma unroll 4
     for (int64_t r = r0 + g.rsub; r < r1; r += g.RPI) {
       float v[4];
       load4(z + r * C + g.cg * 4, v);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float d = v[q] - K[q];
+        const float d = v[q] - m[q];
         s1[q] += d;
         s2[q] += d * d;
       }
@@ -1379,30 +1399,66 @@ __global__ __launch_bounds__(256) void bn_stats_part_kernel(const float *__restr
   if (g.active && g.rsub == 0)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float *p = part + ((int64_t)blockIdx.x * C + g.cg * 4 + q) * 2;
-      p[0] = s1[q];
-      p[1] = s2[q];
+      float *p = part + ((int64_t)blockIdx.x * C + g.cg * 4 + q) * 3;
+      p[0] = m[q];
+      p[1] = s1[q];
+      p[2] = s2[q];
     }
 }
 
-__global__ __launch_bounds__(256) void bn_stats_finish_kernel(const float *__restrict__ z, int64_t R,
-                                                              const float *__restrict__ part, int blocks, int C,
-                                                              float eps, float momentum, float *running_mean,
-                                                              float *running_var, float *__restrict__ mean_out,
+// The blocks' (n_b, mean_b, M2_b) merged in double, in block order (deterministic):
+//   mu = sum_b (n_b m_b + s1_b) / R,    M2 = sum_b (s2_b + 2 (m_b - mu) s1_b + n_b (m_b - mu)^2)
+// which is sum_b [M2_b + n_b (mean_b - mu)^2] (Chan's combination) with mean_b = m_b + s1_b / n_b and
+// M2_b = s2_b - s1_b^2 / n_b, written without the per-block divisions. 256 threads = 16 block groups x
+// 16 channels: group g loads the partials of blocks 16 g .. 16 g + 15 once (every load issued before
+// the first add; both sums use them from registers), the 16 group sums are added in group order.
+__global__ __launch_bounds__(256) void bn_stats_finish_kernel(int64_t R, const float *__restrict__ part, int blocks,
+                                                              int rpb, int C, float eps, float momentum,
+                                                              float *running_mean, float *running_var,
+                                                              float *__restrict__ mean_out,
                                                               float *__restrict__ rstd_out) {
-  __shared__ float sv[2][64];
-  const int64_t col = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);  // c * 2 + j
-  const float v = parts_col_sum(part, blocks, 2LL * C, col);
-  if (threadIdx.x < 64) sv[col & 1][threadIdx.x >> 1] = v;  // (sum, sum of squares) of channel col / 2
-  __syncthreads();
-  if (threadIdx.x >= 32) return;
-  const int c = blockIdx.x * 32 + threadIdx.x;
-  if (c >= C) return;
-  const double n = (double)R, m1 = (double)sv[0][threadIdx.x] / n;
-  const double var = fmax((double)sv[1][threadIdx.x] / n - m1 * m1, 0.0);
-  const float mean = z[c] + (float)m1;
+  static_assert(kBnBlocks == 16 * 16, "16 block groups x 16 partial blocks");
+  __shared__ double red[16][16];
+  const int bg = threadIdx.x >> 4, cl = threadIdx.x & 15;
+  const int c = blockIdx.x * 16 + cl;
+  float pm[16], p1[16], p2[16];
+  double nb[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int b = bg * 16 + k;
+    const bool on = c < C && b < blocks;
+    const float *p = part + ((int64_t)b * C + c) * 3;
+    pm[k] = on ? p[0] : 0.f;
+    p1[k] = on ? p[1] : 0.f;
+    p2[k] = on ? p[2] : 0.f;
+    const int64_t left = R - (int64_t)b * rpb;
+    nb[k] = (double)(left < 0 ? 0 : (left < rpb ? left : rpb));
+  }
+  auto group_sum = [&](double v) {  // every thread calls it; the result is the channel's total
+    __syncthreads();
+    red[bg][cl] = v;
+    __syncthreads();
+    double t = red[0][cl];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) t += red[g][cl];
+    return t;
+  };
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) s += nb[k] * (double)pm[k] + (double)p1[k];
+  const double n = (double)R;
+  const double mu = group_sum(s) / n;
+  double m2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const double e = (double)pm[k] - mu;
+    m2 += (double)p2[k] + 2.0 * e * (double)p1[k] + nb[k] * e * e;
+  }
+  const double var = fmax(group_sum(m2) / n, 0.0);
+  if (bg != 0 || c >= C) return;
+  const float mean = (float)mu;
   mean_out[c] = mean;
-  rstd_out[c] = rsqrtf((float)var + eps);
+  rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
   if (running_mean != nullptr) {
     running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
     running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)(var * n / (n > 1.0 ? n - 1.0 : 1.0));
@@ -1583,7 +1639,7 @@ extern "C" int fs2_bn_train_fwd(const float *z, int64_t R, int C, const float *g
   const int nb = bn_blocks(R, &rpb);
   const size_t lds = (size_t)(256 / (C >> 2)) * C * sizeof(float);
   hipLaunchKernelGGL(bn_stats_part_kernel, dim3(nb), dim3(256), lds, s, z, R, C, rpb, ws);
-  hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((2 * C + 63) / 64), dim3(256), 0, s, z, R, ws, nb, C, eps, momentum,
+  hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((C + 15) / 16), dim3(256), 0, s, R, ws, nb, rpb, C, eps, momentum,
                      running_mean, running_var, mean, rstd);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_grid(R, C)), dim3(256), 0, s, z, R, C, mean, rstd, gamma, beta, use_tanh,
                      drop_threshold(p_drop), 1.0f / (1.0f - p_drop), seed, (uint32_t)salt, residual,
