@@ -13,13 +13,13 @@ FRAMES, D = 24883, 256
 
 def main(table, source):
     rows = json.load(open(table))
-    ffn = [r for r in rows if "ffn_fused_kernel<9, 4, 7, true>" in r["name"]]  # the decoder PRE launches
+    ffn = [r for r in rows if "ffn_fused_kernel<9, 4, 7, true" in r["name"]]  # the decoder PRE launches, 4 or 8 waves
     last, rest = ffn[-1], ffn[:-1]
     algo = {"att_rows_in": FRAMES * D * 2, "x_rows_in": FRAMES * D * 2, "y_rows_out": FRAMES * D * 2,
             "weights_once": 2 * (256 * 256 + 256 * 9 * 1024 + 1024 * 256)}
     hbm = (2 * last["FETCH_SIZE"] + last["WRITE_SIZE"]) * 1024
     out = {
-        "kernel": "ffn_fused_kernel<9,4,7,PRE=true> (decoder's last block: fc + residual + LN prologue, FFN, LN "
+        "kernel": "ffn_fused_kernel<9,4,7,PRE=true,NW=4|8> (decoder's last block: fc + residual + LN prologue, FFN, LN "
                   "epilogue; the bench line's roofline launch)",
         "launch_position": last["pos"],
         "FETCH_SIZE_KiB": last["FETCH_SIZE"],
