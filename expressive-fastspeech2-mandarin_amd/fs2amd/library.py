@@ -33,6 +33,9 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   ``state``) and ``fs2::normalize_minmax(values, lens, mean, std) -> (out, minmax)`` — the corpus
   preprocessing of preprocessor/preprocessor.py:263-291, :367-375, :152-155 and :377-388
   (include/fs2hip_prep.h), float64 results.
+* ``fs2::f0_yin(wav, lens, sampling_rate, hop, win, f0_floor, f0_ceil, threshold) -> (f0, tau, cmnd)`` —
+  the F0 contour of a ragged waveform batch (include/fs2hip_f0.h: YIN in float64, not the reference's
+  pyworld call): f0 f64 [B, n_max // hop + 1], tau int32 likewise, cmnd f64 [B, n_max // hop + 1, tau_max + 1].
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -240,3 +243,22 @@ def _normalize_minmax_fake(values, lens, mean, std):
 OPS = ("length_regulate", "attention", "attention_bwd", "ffn", "conv1d", "mel_spectrogram", "stft", "istft")
 # the corpus preprocessing ops (include/fs2hip_prep.h), listed on their own: OPS is the model's and the audio path's
 OPS_PREP = ("pitch_targets", "outlier_moments", "moments_merge", "normalize_minmax")
+
+
+@torch.library.custom_op("fs2::f0_yin", mutates_args=())
+def f0_yin(wav: Tensor, lens: Optional[Tensor], sampling_rate: float, hop: int, win: int, f0_floor: float,
+           f0_ceil: float, threshold: float) -> Tuple[Tensor, Tensor, Tensor]:
+    return tuple(ops.f0_yin(wav, lens, sampling_rate=sampling_rate, hop_length=hop, win_length=win, f0_floor=f0_floor,
+                            f0_ceil=f0_ceil, threshold=threshold, want_cmnd=True))
+
+
+@f0_yin.register_fake
+def _f0_yin_fake(wav, lens, sampling_rate, hop, win, f0_floor, f0_ceil, threshold):
+    B, n_max = wav.shape
+    F_max = n_max // hop + 1
+    return (wav.new_empty(B, F_max, dtype=torch.float64), wav.new_empty(B, F_max, dtype=torch.int32),
+            wav.new_empty(B, F_max, ops.f0_lags(sampling_rate, f0_floor, f0_ceil)[1] + 1, dtype=torch.float64))
+
+
+# the F0 estimator (include/fs2hip_f0.h), on its own as OPS_PREP is
+OPS_F0 = ("f0_yin",)

@@ -2111,3 +2111,51 @@ def normalize_minmax(values, lens=None, *, mean, std, out=None, workspace=None):
                                       _ptr(o), _ptr(mm), _ptr(workspace), workspace.numel() * workspace.element_size(),
                                       _stream(values)), "fs2_normalize_minmax")
     return o, mm
+
+
+F0Out = collections.namedtuple("F0Out", "f0 tau cmnd")
+
+
+def f0_lags(sampling_rate, f0_floor, f0_ceil):
+    """(tau_min, tau_max) of include/fs2hip_f0.h: floor(sr / f0_ceil) and ceil(sr / f0_floor)."""
+    import math
+
+    return int(math.floor(float(sampling_rate) / float(f0_ceil))), int(math.ceil(float(sampling_rate) / float(f0_floor)))
+
+
+def f0_yin(wav, lens=None, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.0, f0_ceil=800.0, threshold=0.1,
+           want_tau=True, want_cmnd=False, out=None):
+    """fs2_f0_yin (include/fs2hip_f0.h): wav int16 or float32 [B, n_max] (unit sample stride, any row
+    stride; ragged through lens [B]) -> F0Out(f0 f64 [B, F_max] with F_max = n_max // hop + 1, one
+    value per hop at sample k * hop, 0 = unvoiced and 0 past lens // hop + 1; tau int32 [B, F_max]
+    the picked lag (None unless want_tau); cmnd f64 [B, F_max, tau_max + 1] the normalised
+    difference table the pick compared (None unless want_cmnd)). YIN in float64, not WORLD's DIO +
+    StoneMask: see the header. out: (f0, tau or None, cmnd or None) buffers to write into."""
+    _gpu(wav)
+    if wav.dim() != 2 or wav.dtype not in (torch.int16, torch.float32) or wav.shape[1] < 1 or wav.stride(1) != 1:
+        raise ValueError("fs2amd: wav must be an int16 or float32 [B, n_max >= 1] tensor with unit sample stride")
+    B, n_max = wav.shape
+    hop, W = int(hop_length), int(win_length)
+    tau_min, tau_max = f0_lags(sampling_rate, f0_floor, f0_ceil)
+    if hop < 1 or W < 1 or tau_min < 2 or tau_min >= tau_max:
+        raise ValueError(f"fs2amd: f0_yin needs hop, win >= 1 and 2 <= tau_min < tau_max, got lags {tau_min}..{tau_max}")
+    need = int(_lib.fs2_f0_lds_bytes(hop, W, tau_max))
+    if need > L.F0_LDS_BYTES:
+        raise ValueError(f"fs2amd: f0_yin stages {need} bytes of LDS for hop {hop}, win {W}, tau_max {tau_max}; the "
+                         f"limit is {L.F0_LDS_BYTES}")
+    stride = wav.stride(0) if B > 1 else n_max
+    if stride < n_max:
+        raise ValueError(f"fs2amd: wav rows overlap (row stride {stride} < {n_max})")
+    lens_dev, _ = _lengths_arg(lens, B, wav.device, "lens")
+    _gpu(lens_dev)
+    F_max = n_max // hop + 1
+    if out is None:
+        f0 = torch.empty(B, F_max, device=wav.device, dtype=torch.float64)
+        tau = torch.empty(B, F_max, device=wav.device, dtype=torch.int32) if want_tau else None
+        cmnd = torch.empty(B, F_max, tau_max + 1, device=wav.device, dtype=torch.float64) if want_cmnd else None
+    else:
+        f0, tau, cmnd = out
+    L.check(_lib.fs2_f0_yin(_ptr(wav), L.FS2_I16 if wav.dtype == torch.int16 else L.FS2_F32, stride, _ptr(lens_dev), B,
+                            n_max, float(sampling_rate), hop, W, tau_min, tau_max, float(threshold), float(f0_floor),
+                            float(f0_ceil), _ptr(f0), _ptr(tau), _ptr(cmnd), _stream(wav)), "fs2_f0_yin")
+    return F0Out(f0, tau, cmnd)

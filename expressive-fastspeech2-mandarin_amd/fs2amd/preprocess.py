@@ -2,6 +2,7 @@
 reference's preprocessor/preprocessor.py does between feature extraction and ``stats.json``.
 
 * ``get_alignment`` — :327-365 over ``(start, end, label)`` intervals (host code).
+* ``f0_contour`` — the contour the reference takes from pyworld (:255-261), here from YIN on the GPU.
 * ``pitch_targets`` — :263-291: crop, interpolate over unvoiced frames, phoneme mean.
 * ``remove_outlier`` / ``CorpusStats`` — :367-375 and the ``StandardScaler.partial_fit`` calls of
   :152-155: the IQR fence per utterance and a running mean / variance kept on the device.
@@ -9,8 +10,12 @@ reference's preprocessor/preprocessor.py does between feature extraction and ``s
 * ``build_corpus`` — the directory layout of :183-222 and :304-325.
 
 The arithmetic runs in the kernels of include/fs2hip_prep.h (float64, uncontracted; see the header
-for what is exact). F0 estimation is not here: the contour per utterance is an input, float64, 0
-where unvoiced, as ``pyworld.stonemask`` returns it. TextGrid files are not read either.
+for what is exact). The F0 contour per utterance, float64 and 0 where unvoiced, is either an input
+(as ``pyworld.stonemask`` returns it) or estimated from the waveform by the kernel of
+include/fs2hip_f0.h. That estimator is YIN, not WORLD's DIO + StoneMask: same time grid, length
+and range, other values, so ``stats.json`` built from it differs from a WORLD-built corpus's and a
+checkpoint should be used with targets from the estimator it was trained on. TextGrid files are
+not read.
 """
 import json
 import os
@@ -87,6 +92,34 @@ def pitch_targets(f0_list, durations, *, device=None, return_filled=False):
         res.append(out[b, :n_ph[b]].copy() if keep else None)
         fil.append(filled[b, :n].copy() if keep else None)
     return (res, fil) if return_filled else res
+
+
+F0_DEFAULTS = {"f0_floor": 71.0, "f0_ceil": 800.0, "threshold": 0.1, "win_length": 1024}
+
+
+def _f0_rows(wav_dev, lens, **kw):
+    """ops.f0_yin over an uploaded batch -> the float64 contours [lens[b] // hop + 1] on the host."""
+    from . import ops
+
+    f0 = ops.f0_yin(wav_dev, torch.from_numpy(np.asarray(lens, dtype=np.int64)), want_tau=False, **kw).f0.cpu().numpy()
+    return [f0[b, :int(n) // int(kw["hop_length"]) + 1].copy() for b, n in enumerate(lens)]
+
+
+def f0_contour(wavs, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.0, f0_ceil=800.0, threshold=0.1,
+               device=None):
+    """F0 contours of a list of 1-D int16 / float32 waveforms: a list of float64 arrays of length
+    len(w) // hop_length + 1, one value per hop at sample k * hop_length, 0 where unvoiced: the
+    grid, length and range (71-800 Hz) of the reference's pyworld call, but YIN (include/fs2hip_f0.h),
+    so the values are not WORLD's. A batch with any float32 waveform is processed as float32."""
+    dev = _device(device)
+    wavs = [np.asarray(w) for w in wavs]
+    if any(w.ndim != 1 or w.dtype not in (np.int16, np.float32) for w in wavs):
+        raise ValueError("fs2amd: waveforms are 1-D int16 or float32 arrays")
+    if not wavs:
+        return []
+    wav, lens = _pack(wavs, np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32)
+    return _f0_rows(torch.from_numpy(wav).to(dev), lens, sampling_rate=sampling_rate, hop_length=hop_length,
+                    win_length=win_length, f0_floor=f0_floor, f0_ceil=f0_ceil, threshold=threshold)
 
 
 def _fence(arrays, dev):
@@ -176,6 +209,10 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
     int16), ``f0`` (float64 contour at the STFT's hop, 0 = unvoiced) and ``durations`` (frames per
     phoneme). stft: a fs2amd.audio.TacotronSTFT on the GPU. val_size: None = the configuration's.
+    An utterance without ``f0`` (or with None) gets its contour from ``ops.f0_yin`` over the batch
+    already uploaded for the features, at the configuration's sampling rate and hop, with the
+    defaults of ``f0_contour`` unless preprocess_config["preprocessing"]["pitch_extraction"] sets
+    ``f0_floor`` / ``f0_ceil`` / ``threshold`` / ``win_length``.
 
     Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
     batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
@@ -197,6 +234,7 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
             raise ValueError(f"fs2amd: unknown feature level {feat!r}")
     for kind in ("mel", "pitch", "energy", "duration"):
         os.makedirs(os.path.join(out_dir, kind), exist_ok=True)
+    f0_kw = dict(F0_DEFAULTS, **pp.get("pitch_extraction", {}))
     pitch_stats, energy_stats = CorpusStats(dev), CorpusStats(dev)
     speakers, lines, kept = {}, [], []  # kept: (speaker, basename, pitch, energy)
 
@@ -205,8 +243,14 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
         wdtype = np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32
         wav, lens = _pack(wavs, wdtype)
         durs = [np.asarray(u["durations"], dtype=np.int64) for u in batch]
-        feats = extract_features(torch.from_numpy(wav).to(dev), lens, durs, stft=stft)
-        f0s = [np.asarray(u["f0"], dtype=np.float64) for u in batch]
+        wav_dev = torch.from_numpy(wav).to(dev)
+        feats = extract_features(wav_dev, lens, durs, stft=stft)
+        f0s = [u.get("f0") for u in batch]
+        if any(f is None for f in f0s):
+            est = _f0_rows(wav_dev, lens, sampling_rate=pp["audio"]["sampling_rate"],
+                           hop_length=pp["stft"]["hop_length"], **f0_kw)
+            f0s = [e if f is None else f for f, e in zip(f0s, est)]
+        f0s = [np.asarray(f, dtype=np.float64) for f in f0s]
         ph = pitch_targets(f0s, durs, device=dev)
         pitches, energies = [], []
         for b, u in enumerate(batch):
