@@ -20,6 +20,7 @@ FS2_I16 = 3  # include/fs2hip_audio.h: int16 PCM, waveform input only
 FS2_F64 = 4  # include/fs2hip_prep.h: IEEE double, the preprocessing entry points only
 PITCH_T_MAX, PITCH_T_MAX_NOFILL, OUTLIER_LDS_BYTES = 131072, 4096, 65536  # FS2_PITCH_T_MAX, ..., of the same header
 F0_GROUP, F0_LDS_BYTES = 8, 65536  # include/fs2hip_f0.h: FS2_F0_GROUP, FS2_F0_LDS_BYTES
+RESAMPLE_LDS_BYTES = 81920  # include/fs2hip_resample.h: FS2_RESAMPLE_LDS_BYTES
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -332,6 +333,15 @@ SIGNATURES_F0 = {
 }
 
 
+# include/fs2hip_resample.h: raw audio -> resampled f64 / f32 rows with their peak -> int16
+SIGNATURES_RESAMPLE = {
+    "fs2_resample_out_len": (_i64, [_i64, _i64, _i64]),
+    "fs2_resample_lds_bytes": (_i64, [_i64, _i64]),
+    "fs2_resample": (_i, [_p, _i, _i64, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "fs2_peak_int16": (_i, [_p, _p, _p, _i, _i, _f, _p, _p]),
+}
+
+
 def f0_dp_ulps(W, tau):
     """FS2_F0_DP_ULPS of the same header: the bound on dp's relative error, in units of 2^-53."""
     return 2 * W + tau + 6
@@ -354,7 +364,9 @@ HEADER_AUDIO = os.path.join(os.path.dirname(HEADER), "fs2hip_audio.h")
 HEADER_AUDIO_INV = os.path.join(os.path.dirname(HEADER), "fs2hip_audio_inv.h")
 HEADER_PREP = os.path.join(os.path.dirname(HEADER), "fs2hip_prep.h")
 HEADER_F0 = os.path.join(os.path.dirname(HEADER), "fs2hip_f0.h")
-EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h")
+HEADER_RESAMPLE = os.path.join(os.path.dirname(HEADER), "fs2hip_resample.h")
+EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
+                 "fs2hip_resample.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -400,7 +412,7 @@ def load():
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
-            list(SIGNATURES_F0.items()):
+            list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -399,3 +399,29 @@ def mel_to_wav(mel, mel_lens, stft, n_iters=60, angles=None):
 
     wav, _ = ops.griffin_lim(mag.to(dev), frames, stft=stft, n_iters=n_iters, angles=angles)
     return wav, (stft.hop_length * (frames - 1)).numpy()
+
+
+def resample_ratio(target_rate, source_rate):
+    """(up, down) of include/fs2hip_resample.h: target / g and source / g with g their gcd."""
+    import math
+
+    target_rate, source_rate = int(target_rate), int(source_rate)
+    if target_rate < 1 or source_rate < 1:
+        raise ValueError(f"fs2amd: sampling rates must be positive integers, got {source_rate} -> {target_rate}")
+    g = math.gcd(target_rate, source_rate)
+    return target_rate // g, source_rate // g
+
+
+def resample_taps(up, down, beta=5.0):
+    """The low-pass of scipy.signal.resample_poly's default design, float64, in numpy alone: with
+    half = 10 * max(up, down) and c = 1 / max(up, down), the 2 * half + 1 taps
+    c * sinc(c * (k - half)) * kaiser(beta), divided by their sum (include/fs2hip_resample.h).
+    The kernel takes ``resample_taps(up, down) * up``. np.kaiser and scipy's window use different
+    fits of i0, so the taps are scipy's firwin to a few 1e-16 of the largest tap, not bit for bit."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"fs2amd: resample_taps needs up, down >= 1, got {up}, {down}")
+    half = 10 * max(up, down)
+    c = 1.0 / max(up, down)
+    h = c * np.sinc(c * (np.arange(2 * half + 1, dtype=np.float64) - half)) * np.kaiser(2 * half + 1, float(beta))
+    return h / h.sum()

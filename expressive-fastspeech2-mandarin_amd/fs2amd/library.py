@@ -36,6 +36,10 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
 * ``fs2::f0_yin(wav, lens, sampling_rate, hop, win, f0_floor, f0_ceil, threshold) -> (f0, tau, cmnd)`` —
   the F0 contour of a ragged waveform batch (include/fs2hip_f0.h: YIN in float64, not the reference's
   pyworld call): f0 f64 [B, n_max // hop + 1], tau int32 likewise, cmnd f64 [B, n_max // hop + 1, tau_max + 1].
+* ``fs2::resample(wav, lens, taps, up, down) -> (y, y32, peak, out_lens)`` and ``fs2::peak_int16(y32, peak,
+  out_lens, max_wav_value) -> int16 rows`` — the reference's prepare_align arithmetic
+  (preprocessor/esd_chinese.py:145-147) over a ragged batch (include/fs2hip_resample.h): y f64
+  [B, ceil(n_max * up / down)] bit for bit scipy.signal.resample_poly's, y32 its f32 rounding, peak f32 [B].
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -262,3 +266,31 @@ def _f0_yin_fake(wav, lens, sampling_rate, hop, win, f0_floor, f0_ceil, threshol
 
 # the F0 estimator (include/fs2hip_f0.h), on its own as OPS_PREP is
 OPS_F0 = ("f0_yin",)
+
+
+@torch.library.custom_op("fs2::resample", mutates_args=())
+def resample(wav: Tensor, lens: Optional[Tensor], taps: Optional[Tensor], up: int,
+             down: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    return tuple(ops.resample(wav, lens, up=up, down=down, taps=taps))
+
+
+@resample.register_fake
+def _resample_fake(wav, lens, taps, up, down):
+    B, n_max = wav.shape
+    M_max = (n_max * up + down - 1) // down
+    return (wav.new_empty(B, M_max, dtype=torch.float64), wav.new_empty(B, M_max, dtype=torch.float32),
+            wav.new_empty(B, dtype=torch.float32), wav.new_empty(B, dtype=torch.int64))
+
+
+@torch.library.custom_op("fs2::peak_int16", mutates_args=())
+def peak_int16(y32: Tensor, peak: Tensor, out_lens: Optional[Tensor], max_wav_value: float) -> Tensor:
+    return ops.peak_int16(y32, peak, out_lens, max_wav_value=max_wav_value)
+
+
+@peak_int16.register_fake
+def _peak_int16_fake(y32, peak, out_lens, max_wav_value):
+    return y32.new_empty(y32.shape, dtype=torch.int16)
+
+
+# the resampler and the peak normalisation (include/fs2hip_resample.h), on their own as OPS_F0 is
+OPS_RESAMPLE = ("resample", "peak_int16")

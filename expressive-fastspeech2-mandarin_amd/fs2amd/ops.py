@@ -2159,3 +2159,85 @@ def f0_yin(wav, lens=None, *, sampling_rate, hop_length, win_length=1024, f0_flo
                             n_max, float(sampling_rate), hop, W, tau_min, tau_max, float(threshold), float(f0_floor),
                             float(f0_ceil), _ptr(f0), _ptr(tau), _ptr(cmnd), _stream(wav)), "fs2_f0_yin")
     return F0Out(f0, tau, cmnd)
+
+
+ResampleOut = collections.namedtuple("ResampleOut", "y y32 peak out_lens")
+
+
+def resample_out_len(n, up, down):
+    """ceil(n * up / down) of include/fs2hip_resample.h (scipy.signal.resample_poly's length), 0 for n < 1."""
+    n, up, down = int(n), int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"fs2amd: resample needs up, down >= 1, got {up}, {down}")
+    return -(-n * up // down) if n > 0 else 0
+
+
+def resample(wav, lens=None, *, up, down, taps=None, want_y=True, out=None):
+    """fs2_resample (include/fs2hip_resample.h): wav int16 or float32 [B, n_max] (unit sample stride,
+    any row stride; ragged through lens [B]) resampled by up / down with the float64 taps
+    h = resample_taps(up, down) * up (a device tensor of 20 * max(up, down) + 1 values; not needed
+    when up == down == 1) -> ResampleOut(y f64 [B, M_max] with M_max = ceil(n_max * up / down), bit
+    for bit scipy.signal.resample_poly's output (None unless want_y); y32 f32 [B, M_max] its
+    rounding; peak f32 [B] = max |y32|; out_lens int64 [B] = ceil(lens * up / down)). Rows are 0
+    past out_lens. out: (y or None, y32, peak, out_lens) buffers to write into."""
+    _gpu(wav, taps)
+    if wav.dim() != 2 or wav.dtype not in (torch.int16, torch.float32) or wav.shape[1] < 1 or wav.stride(1) != 1:
+        raise ValueError("fs2amd: wav must be an int16 or float32 [B, n_max >= 1] tensor with unit sample stride")
+    B, n_max = wav.shape
+    up, down = int(up), int(down)
+    M_max = resample_out_len(n_max, up, down)
+    fir = not (up == 1 and down == 1)
+    n_taps = 20 * max(up, down) + 1
+    if fir:
+        need = int(_lib.fs2_resample_lds_bytes(up, down))
+        if need > L.RESAMPLE_LDS_BYTES:
+            raise ValueError(f"fs2amd: resample stages {need} bytes of taps in LDS for {up}/{down}; the limit is "
+                             f"{L.RESAMPLE_LDS_BYTES}")
+        if taps is None or taps.dtype != torch.float64 or taps.shape != (n_taps,) or not taps.is_contiguous():
+            raise ValueError(f"fs2amd: taps must be a contiguous float64 [{n_taps}] tensor for {up}/{down}")
+    if M_max > 2 ** 31 - 1:
+        raise ValueError(f"fs2amd: resample writes at most 2^31 - 1 samples per utterance, got {M_max}")
+    stride = wav.stride(0) if B > 1 else n_max
+    if stride < n_max:
+        raise ValueError(f"fs2amd: wav rows overlap (row stride {stride} < {n_max})")
+    lens_dev, _ = _lengths_arg(lens, B, wav.device, "lens")
+    _gpu(lens_dev)
+    if out is None:
+        y = torch.empty(B, M_max, device=wav.device, dtype=torch.float64) if want_y else None
+        y32 = torch.empty(B, M_max, device=wav.device, dtype=torch.float32)
+        peak = torch.empty(B, device=wav.device, dtype=torch.float32)
+        out_lens = torch.empty(B, device=wav.device, dtype=torch.int64)
+    else:
+        y, y32, peak, out_lens = out
+        for t, dt, shape in ((y, torch.float64, (B, M_max)), (y32, torch.float32, (B, M_max)),
+                             (peak, torch.float32, (B,)), (out_lens, torch.int64, (B,))):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"fs2amd: resample out buffers must be contiguous {dt} {list(shape)}")
+        _gpu(y, y32, peak, out_lens)
+        if y32 is None or peak is None:
+            raise ValueError("fs2amd: resample needs the y32 and peak buffers")
+    L.check(_lib.fs2_resample(_ptr(wav), L.FS2_I16 if wav.dtype == torch.int16 else L.FS2_F32, stride, _ptr(lens_dev), B,
+                              n_max, up, down, _ptr(taps) if fir else None, n_taps, _ptr(y), _ptr(y32), _ptr(peak),
+                              _ptr(out_lens), _stream(wav)), "fs2_resample")
+    return ResampleOut(y, y32, peak, out_lens)
+
+
+def peak_int16(y32, peak, out_lens=None, *, max_wav_value=32768.0, out=None):
+    """fs2_peak_int16 (include/fs2hip_resample.h): y32 f32 [B, M_max], peak f32 [B], out_lens [B] (None:
+    M_max each) -> int16 [B, M_max]: trunc((y32 / peak) * max_wav_value) in float32, saturated to
+    [-32768, 32767]; 0 past out_lens and where peak is 0. out: the buffer to write into."""
+    _gpu(y32, peak)
+    if y32.dim() != 2 or y32.dtype != torch.float32 or y32.shape[1] < 1 or not y32.is_contiguous():
+        raise ValueError("fs2amd: y32 must be a contiguous float32 [B, M_max >= 1] tensor")
+    B, M_max = y32.shape
+    if peak.dtype != torch.float32 or peak.shape != (B,) or not peak.is_contiguous():
+        raise ValueError(f"fs2amd: peak must be a contiguous float32 [{B}] tensor")
+    lens_dev, _ = _lengths_arg(out_lens, B, y32.device, "out_lens")
+    _gpu(lens_dev)
+    if out is None:
+        out = torch.empty(B, M_max, device=y32.device, dtype=torch.int16)
+    elif out.dtype != torch.int16 or out.shape != (B, M_max) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"fs2amd: out must be a contiguous int16 [{B}, {M_max}] device tensor")
+    L.check(_lib.fs2_peak_int16(_ptr(y32), _ptr(peak), _ptr(lens_dev), B, M_max, float(max_wav_value), _ptr(out),
+                                _stream(y32)), "fs2_peak_int16")
+    return out

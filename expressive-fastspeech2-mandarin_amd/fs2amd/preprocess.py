@@ -2,6 +2,8 @@
 reference's preprocessor/preprocessor.py does between feature extraction and ``stats.json``.
 
 * ``get_alignment`` — :327-365 over ``(start, end, label)`` intervals (host code).
+* ``prepare_wavs`` — the prepare_align step before it (preprocessor/esd_chinese.py:145-147): raw audio
+  at any rate to peak-normalised int16 at the configuration's (include/fs2hip_resample.h).
 * ``f0_contour`` — the contour the reference takes from pyworld (:255-261), here from YIN on the GPU.
 * ``pitch_targets`` — :263-291: crop, interpolate over unvoiced frames, phoneme mean.
 * ``remove_outlier`` / ``CorpusStats`` — :367-375 and the ``StandardScaler.partial_fit`` calls of
@@ -122,6 +124,43 @@ def f0_contour(wavs, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.
                     win_length=win_length, f0_floor=f0_floor, f0_ceil=f0_ceil, threshold=threshold)
 
 
+def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=None):
+    """The reference's prepare_align arithmetic (preprocessor/esd_chinese.py:145-147) for a list of
+    1-D int16 / float32 waveforms at the source rates ``rates`` (one per waveform, or one number for
+    all): resampled to ``sampling_rate``, divided by the peak, scaled by max_wav_value and cut to
+    int16. Returns a list of int16 arrays of ceil(len * up / down) samples, in input order. One
+    ops.resample + ops.peak_int16 pair per distinct source rate; a waveform already at
+    ``sampling_rate`` is only peak-normalised, as the reference does to every file. The resampler is
+    scipy.signal.resample_poly's (include/fs2hip_resample.h), not librosa's soxr_hq; a positive peak
+    comes out as 32767 where the reference's cast wraps. An all-zero waveform stays zero."""
+    from . import ops
+    from .audio import resample_ratio, resample_taps
+
+    dev = _device(device)
+    wavs = [np.asarray(w) for w in wavs]
+    if any(w.ndim != 1 or w.dtype not in (np.int16, np.float32) for w in wavs):
+        raise ValueError("fs2amd: waveforms are 1-D int16 or float32 arrays")
+    rates = [rates] * len(wavs) if np.ndim(rates) == 0 else list(rates)
+    if len(rates) != len(wavs):
+        raise ValueError("fs2amd: one source rate per waveform")
+    groups = {}  # source rate -> indices, in order of first appearance
+    for b, r in enumerate(rates):
+        if int(r) != r:
+            raise ValueError(f"fs2amd: sampling rates must be integers, got {r!r}")
+        groups.setdefault(int(r), []).append(b)
+    res = [None] * len(wavs)
+    for rate, idx in groups.items():
+        up, down = resample_ratio(sampling_rate, rate)
+        group = [wavs[b] for b in idx]
+        wav, lens = _pack(group, np.int16 if all(w.dtype == np.int16 for w in group) else np.float32)
+        taps = None if up == down == 1 else torch.from_numpy(resample_taps(up, down) * up).to(dev)
+        o = ops.resample(torch.from_numpy(wav).to(dev), torch.from_numpy(lens), up=up, down=down, taps=taps, want_y=False)
+        q = ops.peak_int16(o.y32, o.peak, o.out_lens, max_wav_value=max_wav_value).cpu().numpy()
+        for j, b in enumerate(idx):
+            res[b] = q[j, :ops.resample_out_len(int(lens[j]), up, down)].copy()
+    return res
+
+
 def _fence(arrays, dev):
     """ops.outlier_moments over a list of tracks: (OutlierOut, host lens, packed device values)."""
     from . import ops
@@ -213,6 +252,11 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     already uploaded for the features, at the configuration's sampling rate and hop, with the
     defaults of ``f0_contour`` unless preprocess_config["preprocessing"]["pitch_extraction"] sets
     ``f0_floor`` / ``f0_ceil`` / ``threshold`` / ``win_length``.
+    Three more optional keys: ``sampling_rate``, the rate of ``wav`` when it is raw audio: such an
+    utterance goes through ``prepare_wavs`` first (resampled to the configuration's rate and
+    peak-normalised to int16); ``start`` / ``end`` in seconds: the waveform (prepared or not) is cut
+    to ``[int(sr * start):int(sr * end)]`` as preprocessor.py:247-249 does, and ``durations`` and
+    ``f0`` refer to the cut waveform. An utterance with none of them is processed as it is.
 
     Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
     batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
@@ -235,11 +279,28 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     for kind in ("mel", "pitch", "energy", "duration"):
         os.makedirs(os.path.join(out_dir, kind), exist_ok=True)
     f0_kw = dict(F0_DEFAULTS, **pp.get("pitch_extraction", {}))
+    sr = pp["audio"]["sampling_rate"]
     pitch_stats, energy_stats = CorpusStats(dev), CorpusStats(dev)
     speakers, lines, kept = {}, [], []  # kept: (speaker, basename, pitch, energy)
 
-    def flush(batch):
+    def raw_wavs(batch):
+        """The batch's waveforms at the configuration's rate: prepare_wavs for the utterances that
+        name their own rate, then the alignment's cut (preprocessor.py:247-249)."""
         wavs = [np.asarray(u["wav"]) for u in batch]
+        own = [b for b, u in enumerate(batch) if u.get("sampling_rate") is not None]
+        if own:
+            ready = prepare_wavs([wavs[b] for b in own], [batch[b]["sampling_rate"] for b in own], sampling_rate=sr,
+                                 max_wav_value=pp["audio"].get("max_wav_value", 32768.0), device=dev)
+            for b, w in zip(own, ready):
+                wavs[b] = w
+        for b, u in enumerate(batch):
+            start, end = u.get("start"), u.get("end")
+            if start is not None or end is not None:
+                wavs[b] = wavs[b][None if start is None else int(sr * start):None if end is None else int(sr * end)]
+        return wavs
+
+    def flush(batch):
+        wavs = raw_wavs(batch)
         wdtype = np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32
         wav, lens = _pack(wavs, wdtype)
         durs = [np.asarray(u["durations"], dtype=np.int64) for u in batch]
