@@ -3,6 +3,7 @@
     from fs2amd import FastSpeech2          # drop-in for the reference model/fastspeech2.py
     from fs2amd import TacotronSTFT         # drop-in for the reference audio/stft.py (mel / energy targets)
 """
+from .align import AlignmentEncoder, ForwardSumLoss, fit_aligner, mas_durations
 from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, griffin_lim, inv_mel_spec, mel_filterbank,
                     mel_to_wav, window_sumsquare)
 from .loss import FastSpeech2Loss
@@ -14,4 +15,5 @@ from .preprocess import (CorpusStats, build_corpus, f0_contour, get_alignment, n
 __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator", "TacotronSTFT",
            "get_mel_from_wav", "extract_features", "mel_filterbank", "STFT", "griffin_lim", "inv_mel_spec",
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
-           "normalize", "build_corpus", "f0_contour", "prepare_wavs"]
+           "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
+           "mas_durations", "fit_aligner"]

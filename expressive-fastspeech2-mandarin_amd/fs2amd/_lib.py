@@ -21,6 +21,10 @@ FS2_F64 = 4  # include/fs2hip_prep.h: IEEE double, the preprocessing entry point
 PITCH_T_MAX, PITCH_T_MAX_NOFILL, OUTLIER_LDS_BYTES = 131072, 4096, 65536  # FS2_PITCH_T_MAX, ..., of the same header
 F0_GROUP, F0_LDS_BYTES = 8, 65536  # include/fs2hip_f0.h: FS2_F0_GROUP, FS2_F0_LDS_BYTES
 RESAMPLE_LDS_BYTES = 81920  # include/fs2hip_resample.h: FS2_RESAMPLE_LDS_BYTES
+# include/fs2hip_align.h: FS2_MAS_LDS_BYTES, FS2_MAS_LDS_SMALL, FS2_FORWARD_SUM_LDS_BYTES, FS2_MAS_AUTO / _LDS / _GLOBAL
+MAS_LDS_BYTES, MAS_LDS_SMALL, FORWARD_SUM_LDS_BYTES = 163840, 32768, 65536
+MAS_AUTO, MAS_LDS, MAS_GLOBAL = 0, 1, 2
+ALIGN_SIZE_CAP = 1 << 24  # csrc/align_sizes.h: FS2_AL_SIZE_CAP
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -342,6 +346,57 @@ SIGNATURES_RESAMPLE = {
 }
 
 
+# include/fs2hip_align.h: monotonic alignment search, the forward-sum loss and its gradient
+SIGNATURES_ALIGN = {
+    "fs2_mas_lds_bytes": (_i64, [_i, _i, _i]),
+    "fs2_mas_ws_bytes": (_i64, [_i, _i, _i]),
+    "fs2_forward_sum_lds_bytes": (_i64, [_i, _i]),
+    "fs2_mas": (_i, [_p, _i, _i64, _i64, _p, _p, _i, _i, _i, _i, _p, _i64, _p, _p, _p, _p]),
+    "fs2_forward_sum": (_i, [_p, _i, _i64, _i64, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p]),
+    "fs2_forward_sum_bwd": (_i, [_p, _i, _i64, _i64, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p]),
+}
+
+
+def mas_lds_bytes(T_max, L_max, in_lds=True):
+    """The Python mirror of csrc/align_sizes.h (al_mas_lds_bytes): two v rows of L_max + 1 f64, then the
+    decision bitmap of T_max rows of ceil(L_max / 64) 64-bit words when it lives in LDS. 0 for a size
+    below 1, 2^63 - 1 beyond the cap."""
+    if T_max < 1 or L_max < 1:
+        return 0
+    if max(T_max, L_max) > ALIGN_SIZE_CAP:
+        return (1 << 63) - 1
+    return 8 * (2 * (L_max + 1) + (T_max * ((L_max + 63) // 64) if in_lds else 0))
+
+
+def mas_ws_bytes(B, T_max, L_max):
+    """al_mas_ws_bytes: the bitmap of the global form, B * T_max * ceil(L_max / 64) * 8 bytes."""
+    if B < 1 or T_max < 1 or L_max < 1:
+        return 0
+    n = 8 * B * T_max * ((L_max + 63) // 64)
+    return (1 << 63) - 1 if max(B, T_max, L_max) > ALIGN_SIZE_CAP or n > (1 << 63) - 1 else n
+
+
+def forward_sum_lds_bytes(T_max, L_max):
+    """al_fs_lds_bytes: two state rows of 2 L_max + 5 f64, then the max and the log-sum of every frame."""
+    if T_max < 1 or L_max < 1:
+        return 0
+    if max(T_max, L_max) > ALIGN_SIZE_CAP:
+        return (1 << 63) - 1
+    return 8 * (2 * (2 * L_max + 5) + 2 * T_max)
+
+
+def mas_form(T_max, L_max, bitmap=MAS_AUTO):
+    """al_mas_form: (status, MAS_LDS or MAS_GLOBAL or None)."""
+    if T_max < 1 or L_max < 1 or bitmap not in (MAS_AUTO, MAS_LDS, MAS_GLOBAL):
+        return FS2_EINVAL, None
+    if mas_lds_bytes(T_max, L_max, False) > MAS_LDS_BYTES:
+        return FS2_EUNSUPPORTED, None
+    fits = mas_lds_bytes(T_max, L_max, True) <= MAS_LDS_BYTES
+    if bitmap == MAS_LDS and not fits:
+        return FS2_EUNSUPPORTED, None
+    return FS2_OK, MAS_GLOBAL if bitmap == MAS_GLOBAL or not fits else MAS_LDS
+
+
 def f0_dp_ulps(W, tau):
     """FS2_F0_DP_ULPS of the same header: the bound on dp's relative error, in units of 2^-53."""
     return 2 * W + tau + 6
@@ -365,8 +420,9 @@ HEADER_AUDIO_INV = os.path.join(os.path.dirname(HEADER), "fs2hip_audio_inv.h")
 HEADER_PREP = os.path.join(os.path.dirname(HEADER), "fs2hip_prep.h")
 HEADER_F0 = os.path.join(os.path.dirname(HEADER), "fs2hip_f0.h")
 HEADER_RESAMPLE = os.path.join(os.path.dirname(HEADER), "fs2hip_resample.h")
+HEADER_ALIGN = os.path.join(os.path.dirname(HEADER), "fs2hip_align.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
-                 "fs2hip_resample.h")
+                 "fs2hip_resample.h", "fs2hip_align.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -412,7 +468,7 @@ def load():
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
-            list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()):
+            list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -40,6 +40,14 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   out_lens, max_wav_value) -> int16 rows`` — the reference's prepare_align arithmetic
   (preprocessor/esd_chinese.py:145-147) over a ragged batch (include/fs2hip_resample.h): y f64
   [B, ceil(n_max * up / down)] bit for bit scipy.signal.resample_poly's, y32 its f32 rounding, peak f32 [B].
+* ``fs2::mas(logp, mel_lens, text_lens) -> (durations, score, path)`` — monotonic alignment search over
+  attention log-probabilities [B, T_max, L_max] (include/fs2hip_align.h): durations int64 [B, L_max], score
+  f64 [B], path int32 [B, T_max], bit for bit the float64 recurrence; a tie takes the diagonal.
+* ``fs2::forward_sum(logp, mel_lens, text_lens, blank_logprob) -> (loss, nll, alpha)`` — the alignment
+  (CTC) loss of the same header in float64: loss f64 scalar, nll f64 [B], alpha f64 [B, T_max, 2 L_max + 1];
+  differentiable in ``logp`` through ``loss`` (backward: ``fs2::forward_sum_bwd``).
+* ``fs2::forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, grad_out, blank_logprob) -> dlogp`` (logp's
+  dtype, exact zeros outside every utterance's extents).
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -294,3 +302,61 @@ def _peak_int16_fake(y32, peak, out_lens, max_wav_value):
 
 # the resampler and the peak normalisation (include/fs2hip_resample.h), on their own as OPS_F0 is
 OPS_RESAMPLE = ("resample", "peak_int16")
+
+
+@torch.library.custom_op("fs2::mas", mutates_args=())
+def mas(logp: Tensor, mel_lens: Optional[Tensor], text_lens: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    return tuple(ops.mas(logp, mel_lens, text_lens, want_path=True))
+
+
+@mas.register_fake
+def _mas_fake(logp, mel_lens, text_lens):
+    B, T, Lx = logp.shape
+    return (logp.new_empty(B, Lx, dtype=torch.int64), logp.new_empty(B, dtype=torch.float64),
+            logp.new_empty(B, T, dtype=torch.int32))
+
+
+@torch.library.custom_op("fs2::forward_sum", mutates_args=())
+def forward_sum(logp: Tensor, mel_lens: Optional[Tensor], text_lens: Optional[Tensor],
+                blank_logprob: float) -> Tuple[Tensor, Tensor, Tensor]:
+    return tuple(ops.forward_sum(logp, mel_lens, text_lens, blank_logprob=blank_logprob))
+
+
+@forward_sum.register_fake
+def _forward_sum_fake(logp, mel_lens, text_lens, blank_logprob):
+    B, T, Lx = logp.shape
+    return (logp.new_empty((), dtype=torch.float64), logp.new_empty(B, dtype=torch.float64),
+            logp.new_empty(B, T, 2 * Lx + 1, dtype=torch.float64))
+
+
+@torch.library.custom_op("fs2::forward_sum_bwd", mutates_args=())
+def forward_sum_bwd(logp: Tensor, mel_lens: Optional[Tensor], text_lens: Optional[Tensor], alpha: Tensor, nll: Tensor,
+                    grad_out: Tensor, blank_logprob: float) -> Tensor:
+    return ops.forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, grad_out, blank_logprob=blank_logprob)
+
+
+@forward_sum_bwd.register_fake
+def _forward_sum_bwd_fake(logp, mel_lens, text_lens, alpha, nll, grad_out, blank_logprob):
+    return logp.new_empty(logp.shape)
+
+
+def _forward_sum_setup(ctx, inputs, output):
+    logp, mel_lens, text_lens, blank_logprob = inputs
+    _, nll, alpha = output
+    ctx.save_for_backward(logp, mel_lens, text_lens, alpha, nll)
+    ctx.blank_logprob = blank_logprob
+    ctx.set_materialize_grads(False)
+
+
+def _forward_sum_backward(ctx, g_loss, g_nll, g_alpha):
+    if g_loss is None:
+        return None, None, None, None
+    logp, mel_lens, text_lens, alpha, nll = ctx.saved_tensors
+    return torch.ops.fs2.forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, g_loss, ctx.blank_logprob), None, None, None
+
+
+forward_sum.register_autograd(_forward_sum_backward, setup_context=_forward_sum_setup)
+
+
+# monotonic alignment search and the forward-sum loss (include/fs2hip_align.h), on their own as OPS_RESAMPLE is
+OPS_ALIGN = ("mas", "forward_sum", "forward_sum_bwd")

@@ -2241,3 +2241,148 @@ def peak_int16(y32, peak, out_lens=None, *, max_wav_value=32768.0, out=None):
     L.check(_lib.fs2_peak_int16(_ptr(y32), _ptr(peak), _ptr(lens_dev), B, M_max, float(max_wav_value), _ptr(out),
                                 _stream(y32)), "fs2_peak_int16")
     return out
+
+
+MasOut = collections.namedtuple("MasOut", "durations score path")
+ForwardSumOut = collections.namedtuple("ForwardSumOut", "loss nll alpha")
+_MAS_BITMAP = {"auto": L.MAS_AUTO, "lds": L.MAS_LDS, "global": L.MAS_GLOBAL}
+
+
+def _align_args(logp, mel_lens, text_lens, what, *, raise_short):
+    """(dtype code, batch stride, row stride, device mel_lens, device text_lens) of the attention
+    log-probabilities logp [B, T_max, L_max] of fs2_mas / fs2_forward_sum. Host lengths are checked
+    here: beyond the maxima always, and (raise_short) zero or T_b < L_b."""
+    _gpu(logp)
+    if logp.dim() != 3 or logp.dtype not in (torch.float32, torch.float64) or min(logp.shape) < 1:
+        raise ValueError(f"fs2amd: {what} takes a float32 or float64 [B >= 1, T_max >= 1, L_max >= 1] tensor")
+    B, T_max, L_max = logp.shape
+    if L_max > 1 and logp.stride(2) != 1:
+        raise ValueError(f"fs2amd: {what} needs unit stride along the phoneme axis")
+    rs = logp.stride(1) if T_max > 1 else L_max
+    bs = logp.stride(0) if B > 1 else T_max * rs
+    if rs < L_max or bs < (T_max - 1) * rs + L_max:
+        raise ValueError(f"fs2amd: {what}: rows or utterances overlap (row stride {rs}, batch stride {bs})")
+    mel_dev, mel_host = _lengths_arg(mel_lens, B, logp.device, "mel_lens")
+    text_dev, text_host = _lengths_arg(text_lens, B, logp.device, "text_lens")
+    _gpu(mel_dev, text_dev)
+    for host, top, name in ((mel_host, T_max, "mel_lens"), (text_host, L_max, "text_lens")):
+        if host is not None and (int(host.min()) < 0 or int(host.max()) > top):
+            raise ValueError(f"fs2amd: {name} must lie in [0, {top}]")
+    if raise_short:
+        # None stands for the maximum each; device lengths (no host copy) are not checked: no sync
+        th = torch.full((B,), T_max, dtype=torch.int64) if mel_lens is None else mel_host
+        lh = torch.full((B,), L_max, dtype=torch.int64) if text_lens is None else text_host
+        if (th is not None and int(th.min()) < 1) or (lh is not None and int(lh.min()) < 1):
+            raise ValueError(f"fs2amd: {what} needs at least one frame and one phoneme per utterance")
+        if th is not None and lh is not None and bool((th < lh).any()):
+            b = int(torch.nonzero(th < lh)[0])
+            raise ValueError(f"fs2amd: {what}: utterance {b} has {int(th[b])} frames for {int(lh[b])} phonemes; a "
+                             f"monotonic alignment needs T >= L")
+    return (L.FS2_F64 if logp.dtype == torch.float64 else L.FS2_F32), bs, rs, mel_dev, text_dev
+
+
+def mas(logp, mel_lens=None, text_lens=None, *, want_path=False, bitmap="auto", out=None):
+    """fs2_mas (include/fs2hip_align.h): monotonic alignment search over attention log-probabilities
+    logp f32 or f64 [B, T_max, L_max] (unit stride along L, any row and batch stride), ragged through
+    mel_lens [B] and text_lens [B] -> MasOut(durations int64 [B, L_max], frames per phoneme, every
+    entry below L_b >= 1, summing to T_b, 0 beyond L_b; score f64 [B], the best path's log-probability;
+    path int32 [B, T_max], the phoneme of every frame, -1 beyond T_b (None unless want_path)). Bit for
+    bit the float64 recurrence of the header; a tie takes the diagonal. With host lengths an utterance
+    with T_b < L_b or a zero length raises ValueError; with device lengths its row is 0 and its score
+    -inf. bitmap: where the decision bits live, "auto" (LDS where it fits), "lds" or "global": the
+    same bits out. out: (durations, score, path or None) buffers to write into."""
+    code, bs, rs, mel_dev, text_dev = _align_args(logp, mel_lens, text_lens, "mas", raise_short=True)
+    B, T_max, L_max = logp.shape
+    if bitmap not in _MAS_BITMAP:
+        raise ValueError(f"fs2amd: mas bitmap must be one of {sorted(_MAS_BITMAP)}, got {bitmap!r}")
+    rows = int(_lib.fs2_mas_lds_bytes(T_max, L_max, 0))
+    if rows > L.MAS_LDS_BYTES:
+        raise ValueError(f"fs2amd: mas keeps two rows of {L_max} phonemes in {rows} bytes of LDS; the limit is "
+                         f"{L.MAS_LDS_BYTES}")
+    need = int(_lib.fs2_mas_lds_bytes(T_max, L_max, 1))
+    if bitmap == "lds" and need > L.MAS_LDS_BYTES:
+        raise ValueError(f"fs2amd: mas with the bitmap in LDS needs {need} bytes for {T_max} frames x {L_max} "
+                         f"phonemes; the limit is {L.MAS_LDS_BYTES}")
+    in_global = bitmap == "global" or need > L.MAS_LDS_BYTES
+    ws, ws_bytes = None, 0
+    if in_global:
+        ws_bytes = int(_lib.fs2_mas_ws_bytes(B, T_max, L_max))
+        ws = torch.empty(ws_bytes // 8, device=logp.device, dtype=torch.int64)
+    dev = logp.device
+    if out is None:
+        dur = torch.empty(B, L_max, device=dev, dtype=torch.int64)
+        score = torch.empty(B, device=dev, dtype=torch.float64)
+        path = torch.empty(B, T_max, device=dev, dtype=torch.int32) if want_path else None
+    else:
+        dur, score, path = out
+        for t, dt, shape in ((dur, torch.int64, (B, L_max)), (score, torch.float64, (B,)),
+                             (path, torch.int32, (B, T_max))):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"fs2amd: mas out buffers must be contiguous {dt} {list(shape)}")
+        _gpu(dur, score, path)
+        if dur is None or score is None:
+            raise ValueError("fs2amd: mas needs the durations and score buffers")
+    L.check(_lib.fs2_mas(_ptr(logp), code, bs, rs, _ptr(mel_dev), _ptr(text_dev), B, T_max, L_max, _MAS_BITMAP[bitmap],
+                         _ptr(ws), ws_bytes, _ptr(dur), _ptr(score), _ptr(path), _stream(logp)), "fs2_mas")
+    return MasOut(dur, score, path)
+
+
+def _forward_sum_sizes(logp, blank_logprob):
+    import math
+
+    B, T_max, L_max = logp.shape
+    if not math.isfinite(float(blank_logprob)):
+        raise ValueError(f"fs2amd: blank_logprob must be finite, got {blank_logprob!r}")
+    need = int(_lib.fs2_forward_sum_lds_bytes(T_max, L_max))
+    if need > L.FORWARD_SUM_LDS_BYTES:
+        raise ValueError(f"fs2amd: forward_sum needs {need} bytes of LDS for {T_max} frames x {L_max} phonemes; the "
+                         f"limit is {L.FORWARD_SUM_LDS_BYTES}")
+    return B, T_max, L_max
+
+
+def forward_sum(logp, mel_lens=None, text_lens=None, *, blank_logprob=-1.0):
+    """fs2_forward_sum (include/fs2hip_align.h): the alignment loss of attention log-probabilities
+    logp f32 or f64 [B, T_max, L_max] (as ``mas`` takes them): per utterance the CTC negative
+    log-likelihood of "phonemes 1..L_b in order" over log_softmax([blank_logprob, logp[t, :L_b]]), in
+    float64 -> ForwardSumOut(loss f64 scalar = mean over b of nll_b / L_b, nll f64 [B], alpha f64
+    [B, T_max, 2 L_max + 1] for ``forward_sum_bwd``). An utterance with T_b < L_b or a zero length has
+    nll = inf and contributes 0 (zero_infinity)."""
+    code, bs, rs, mel_dev, text_dev = _align_args(logp, mel_lens, text_lens, "forward_sum", raise_short=False)
+    B, T_max, L_max = _forward_sum_sizes(logp, blank_logprob)
+    dev = logp.device
+    alpha = torch.empty(B, T_max, 2 * L_max + 1, device=dev, dtype=torch.float64)
+    nll = torch.empty(B, device=dev, dtype=torch.float64)
+    loss = torch.empty((), device=dev, dtype=torch.float64)
+    L.check(_lib.fs2_forward_sum(_ptr(logp), code, bs, rs, _ptr(mel_dev), _ptr(text_dev), B, T_max, L_max,
+                                 float(blank_logprob), _ptr(alpha), _ptr(nll), _ptr(loss), _stream(logp)),
+            "fs2_forward_sum")
+    return ForwardSumOut(loss, nll, alpha)
+
+
+def forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, grad_out=None, *, blank_logprob=-1.0, out=None):
+    """fs2_forward_sum_bwd: d loss / d logp for the arguments and the (alpha, nll) of ``forward_sum``,
+    times grad_out (a scalar tensor or number; None = 1) -> a contiguous [B, T_max, L_max] tensor of
+    logp's dtype, exact zeros outside [T_b, L_b] and for utterances whose nll is infinite."""
+    code, bs, rs, mel_dev, text_dev = _align_args(logp, mel_lens, text_lens, "forward_sum_bwd", raise_short=False)
+    B, T_max, L_max = _forward_sum_sizes(logp, blank_logprob)
+    dev = logp.device
+    _gpu(alpha, nll)
+    if alpha.dtype != torch.float64 or tuple(alpha.shape) != (B, T_max, 2 * L_max + 1) or not alpha.is_contiguous() \
+            or nll.dtype != torch.float64 or tuple(nll.shape) != (B,) or not nll.is_contiguous():
+        raise ValueError(f"fs2amd: forward_sum_bwd takes alpha float64 [{B}, {T_max}, {2 * L_max + 1}] and nll float64 "
+                         f"[{B}], contiguous, as forward_sum returned them")
+    if grad_out is None or not torch.is_tensor(grad_out):
+        go = torch.full((1,), 1.0 if grad_out is None else float(grad_out), device=dev, dtype=torch.float64)
+    else:
+        _gpu(grad_out)
+        if grad_out.numel() != 1:
+            raise ValueError("fs2amd: grad_out is a scalar")
+        go = grad_out.detach().to(torch.float64).reshape(1).contiguous()
+    if out is None:
+        out = torch.empty(B, T_max, L_max, device=dev, dtype=logp.dtype)
+    elif out.dtype != logp.dtype or tuple(out.shape) != (B, T_max, L_max) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"fs2amd: out must be a contiguous {logp.dtype} [{B}, {T_max}, {L_max}] device tensor")
+    L.check(_lib.fs2_forward_sum_bwd(_ptr(logp), code, bs, rs, _ptr(mel_dev), _ptr(text_dev), B, T_max, L_max,
+                                     float(blank_logprob), _ptr(alpha), _ptr(nll), _ptr(go), _ptr(out), _stream(logp)),
+            "fs2_forward_sum_bwd")
+    return out

@@ -241,8 +241,25 @@ def normalize(arrays, mean, std, *, device=None):
     return [out[b, :lens[b]].copy() for b in range(len(arrays))], vmin, vmax
 
 
+def _aligned_durations(batch, wav_dev, lens, stft, aligner):
+    """The batch's durations: an utterance's own where it brings them, the aligner's over the mel of
+    the uploaded waveform where it does not."""
+    from . import ops
+
+    durs = [u.get("durations") for u in batch]
+    need = [b for b, d in enumerate(durs) if d is None]
+    if need:
+        mel, _, frames = ops.mel_spectrogram(wav_dev, torch.from_numpy(np.asarray(lens, dtype=np.int64)), stft=stft)
+        mel, frames = mel.cpu().numpy(), frames.cpu().numpy()
+        ids = [np.array([aligner.symbols[p] for p in batch[b]["phones"]], dtype=np.int64) for b in need]
+        got = aligner.durations(ids, [mel[b, :int(frames[b])] for b in need])
+        for b, d in zip(need, got):
+            durs[b] = d
+    return [np.asarray(d, dtype=np.int64) for d in durs]
+
+
 def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None, seed=1234, batch_size=16,
-                 emotions=None):
+                 emotions=None, aligner=None):
     """Write a preprocessed corpus directory (preprocessor.py:116-224, :304-325) from utterances, an
     iterable of dicts with ``basename``, ``speaker``, ``phones`` (list of labels), ``raw_text``,
     ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
@@ -257,6 +274,11 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     peak-normalised to int16); ``start`` / ``end`` in seconds: the waveform (prepared or not) is cut
     to ``[int(sr * start):int(sr * end)]`` as preprocessor.py:247-249 does, and ``durations`` and
     ``f0`` refer to the cut waveform. An utterance with none of them is processed as it is.
+    aligner: None, or an object with ``symbols`` (phoneme label -> id) and ``durations(phone_ids_list,
+    mels_list)`` such as ``fs2amd.align.Aligner``: an utterance without ``durations`` (or with None)
+    then gets them from it. The mel of the prepared, cut waveform is computed first, over the batch
+    already uploaded; the aligner's durations sum to its frame count. Utterances that bring
+    ``durations`` go exactly as without an aligner, and a batch may mix both.
 
     Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
     batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
@@ -303,8 +325,11 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
         wavs = raw_wavs(batch)
         wdtype = np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32
         wav, lens = _pack(wavs, wdtype)
-        durs = [np.asarray(u["durations"], dtype=np.int64) for u in batch]
         wav_dev = torch.from_numpy(wav).to(dev)
+        if aligner is None:
+            durs = [np.asarray(u["durations"], dtype=np.int64) for u in batch]
+        else:
+            durs = _aligned_durations(batch, wav_dev, lens, stft, aligner)
         feats = extract_features(wav_dev, lens, durs, stft=stft)
         f0s = [u.get("f0") for u in batch]
         if any(f is None for f in f0s):
