@@ -6,6 +6,7 @@
 from .align import AlignmentEncoder, ForwardSumLoss, fit_aligner, mas_durations
 from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, griffin_lim, inv_mel_spec, mel_filterbank,
                     mel_to_wav, window_sumsquare)
+from .evaluate import dtw, evaluate, f0_metrics, mcd, mel_cepstrum
 from .loss import FastSpeech2Loss
 from .model import FastSpeech2, LengthRegulator
 from .optimizer import ScheduledOptim
@@ -16,4 +17,4 @@ __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator"
            "get_mel_from_wav", "extract_features", "mel_filterbank", "STFT", "griffin_lim", "inv_mel_spec",
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
            "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
-           "mas_durations", "fit_aligner"]
+           "mas_durations", "fit_aligner", "mcd", "dtw", "mel_cepstrum", "f0_metrics", "evaluate"]

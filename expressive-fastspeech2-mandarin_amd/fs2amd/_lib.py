@@ -25,6 +25,10 @@ RESAMPLE_LDS_BYTES = 81920  # include/fs2hip_resample.h: FS2_RESAMPLE_LDS_BYTES
 MAS_LDS_BYTES, MAS_LDS_SMALL, FORWARD_SUM_LDS_BYTES = 163840, 32768, 65536
 MAS_AUTO, MAS_LDS, MAS_GLOBAL = 0, 1, 2
 ALIGN_SIZE_CAP = 1 << 24  # csrc/align_sizes.h: FS2_AL_SIZE_CAP
+# include/fs2hip_eval.h: FS2_DTW_LDS_BYTES, FS2_DTW_LDS_SMALL, FS2_DTW_AUTO / _LDS / _GLOBAL
+DTW_LDS_BYTES, DTW_LDS_SMALL = 163840, 32768
+DTW_AUTO, DTW_LDS, DTW_GLOBAL = 0, 1, 2
+EVAL_SIZE_CAP = 1 << 24  # csrc/eval_sizes.h: FS2_EV_SIZE_CAP
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -397,6 +401,53 @@ def mas_form(T_max, L_max, bitmap=MAS_AUTO):
     return FS2_OK, MAS_GLOBAL if bitmap == MAS_GLOBAL or not fits else MAS_LDS
 
 
+# include/fs2hip_eval.h: mel cepstra, pairwise distances, dynamic time warping, statistics along the path
+SIGNATURES_EVAL = {
+    "fs2_dtw_lds_bytes": (_i64, [_i, _i, _i]),
+    "fs2_dtw_ws_bytes": (_i64, [_i, _i, _i]),
+    "fs2_mel_cepstrum": (_i, [_p, _i, _i64, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "fs2_pair_dist": (_i, [_p, _p, _i, _i64, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "fs2_dtw": (_i, [_p, _p, _i, _i64, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p, _p, _p, _p, _p]),
+    "fs2_path_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+}
+
+
+def dtw_bitmap_words(Tx_max, Ty_max):
+    """ev_dtw_bitmap_words of csrc/eval_sizes.h: two bit planes of ceil(Tx_max / 64) 64-bit words for
+    each of the Tx_max + Ty_max - 1 anti-diagonals."""
+    return (Tx_max + Ty_max - 1) * 2 * ((Tx_max + 63) // 64)
+
+
+def dtw_lds_bytes(Tx_max, Ty_max, in_lds=True):
+    """The Python mirror of csrc/eval_sizes.h (ev_dtw_lds_bytes): three anti-diagonals of Tx_max + 3
+    f64, then the step bitmap when it lives in LDS. 0 for a size below 1, 2^63 - 1 beyond the cap."""
+    if Tx_max < 1 or Ty_max < 1:
+        return 0
+    if max(Tx_max, Ty_max) > EVAL_SIZE_CAP:
+        return (1 << 63) - 1
+    return 8 * (3 * (Tx_max + 3) + (dtw_bitmap_words(Tx_max, Ty_max) if in_lds else 0))
+
+
+def dtw_ws_bytes(B, Tx_max, Ty_max):
+    """ev_dtw_ws_bytes: the bitmap of the global form, B * dtw_bitmap_words * 8 bytes."""
+    if B < 1 or Tx_max < 1 or Ty_max < 1:
+        return 0
+    n = 8 * B * dtw_bitmap_words(Tx_max, Ty_max)
+    return (1 << 63) - 1 if max(B, Tx_max, Ty_max) > EVAL_SIZE_CAP or n > (1 << 63) - 1 else n
+
+
+def dtw_form(Tx_max, Ty_max, bitmap=DTW_AUTO):
+    """ev_dtw_form: (status, DTW_LDS or DTW_GLOBAL or None)."""
+    if Tx_max < 1 or Ty_max < 1 or bitmap not in (DTW_AUTO, DTW_LDS, DTW_GLOBAL):
+        return FS2_EINVAL, None
+    if dtw_lds_bytes(Tx_max, Ty_max, False) > DTW_LDS_BYTES:
+        return FS2_EUNSUPPORTED, None
+    fits = dtw_lds_bytes(Tx_max, Ty_max, True) <= DTW_LDS_BYTES
+    if bitmap == DTW_LDS and not fits:
+        return FS2_EUNSUPPORTED, None
+    return FS2_OK, DTW_GLOBAL if bitmap == DTW_GLOBAL or not fits else DTW_LDS
+
+
 def f0_dp_ulps(W, tau):
     """FS2_F0_DP_ULPS of the same header: the bound on dp's relative error, in units of 2^-53."""
     return 2 * W + tau + 6
@@ -421,8 +472,9 @@ HEADER_PREP = os.path.join(os.path.dirname(HEADER), "fs2hip_prep.h")
 HEADER_F0 = os.path.join(os.path.dirname(HEADER), "fs2hip_f0.h")
 HEADER_RESAMPLE = os.path.join(os.path.dirname(HEADER), "fs2hip_resample.h")
 HEADER_ALIGN = os.path.join(os.path.dirname(HEADER), "fs2hip_align.h")
+HEADER_EVAL = os.path.join(os.path.dirname(HEADER), "fs2hip_eval.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
-                 "fs2hip_resample.h", "fs2hip_align.h")
+                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -468,7 +520,8 @@ def load():
     allow_missing = "FS2_LIB" in os.environ and os.environ.get("FS2_LIB_ALLOW_MISSING") == "1"
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
-            list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()):
+            list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
+            list(SIGNATURES_EVAL.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

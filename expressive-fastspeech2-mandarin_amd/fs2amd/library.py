@@ -48,6 +48,15 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   differentiable in ``logp`` through ``loss`` (backward: ``fs2::forward_sum_bwd``).
 * ``fs2::forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, grad_out, blank_logprob) -> dlogp`` (logp's
   dtype, exact zeros outside every utterance's extents).
+* ``fs2::mel_cepstrum(mel, lens, basis) -> cepstra`` — log-mel [B, T_max, M] times the f64 table basis
+  [C, M] (include/fs2hip_eval.h): f64 [B, T_max, C], summed in index order, zeros past every T_b.
+* ``fs2::pair_dist(x, x_lens, y, y_lens) -> cost`` — Euclidean distances between the frames of
+  x [B, Tx_max, D] and y [B, Ty_max, D] in float64: f64 [B, Tx_max, Ty_max], zeros outside [Tx_b, Ty_b].
+* ``fs2::dtw(x, x_lens, y, y_lens, bitmap) -> (total, K, path_i, path_j)`` — dynamic time warping under
+  that cost: total f64 [B], K int32 [B], path_i / path_j int32 [B, Tx_max + Ty_max - 1] (-1 from K_b on);
+  bitmap 0 / 1 / 2 = auto / LDS / global, the same bits out.
+* ``fs2::path_stats(a, b, path_i, path_j, K) -> (counts, sums)`` — f64 tracks [B, T, Ch] (NaN = absent)
+  read along that path: counts int64 [B, Ch, 4], sums f64 [B, Ch, 2].
 
 Importing this module (``import fs2amd.library``, or the ``model`` drop-in package) registers the ops;
 the C library itself is loaded at the first launch.
@@ -360,3 +369,51 @@ forward_sum.register_autograd(_forward_sum_backward, setup_context=_forward_sum_
 
 # monotonic alignment search and the forward-sum loss (include/fs2hip_align.h), on their own as OPS_RESAMPLE is
 OPS_ALIGN = ("mas", "forward_sum", "forward_sum_bwd")
+
+
+@torch.library.custom_op("fs2::mel_cepstrum", mutates_args=())
+def mel_cepstrum(mel: Tensor, lens: Optional[Tensor], basis: Tensor) -> Tensor:
+    return ops.mel_cepstrum(mel, lens, basis=basis)
+
+
+@mel_cepstrum.register_fake
+def _mel_cepstrum_fake(mel, lens, basis):
+    return mel.new_empty(mel.shape[0], mel.shape[1], basis.shape[0], dtype=torch.float64)
+
+
+@torch.library.custom_op("fs2::pair_dist", mutates_args=())
+def pair_dist(x: Tensor, x_lens: Optional[Tensor], y: Tensor, y_lens: Optional[Tensor]) -> Tensor:
+    return ops.pair_dist(x, x_lens, y, y_lens)
+
+
+@pair_dist.register_fake
+def _pair_dist_fake(x, x_lens, y, y_lens):
+    return x.new_empty(x.shape[0], x.shape[1], y.shape[1], dtype=torch.float64)
+
+
+@torch.library.custom_op("fs2::dtw", mutates_args=())
+def dtw(x: Tensor, x_lens: Optional[Tensor], y: Tensor, y_lens: Optional[Tensor],
+        bitmap: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    return tuple(ops.dtw(x, x_lens, y, y_lens, bitmap=("auto", "lds", "global")[bitmap]))
+
+
+@dtw.register_fake
+def _dtw_fake(x, x_lens, y, y_lens, bitmap):
+    B, P = x.shape[0], x.shape[1] + y.shape[1] - 1
+    return (x.new_empty(B, dtype=torch.float64), x.new_empty(B, dtype=torch.int32),
+            x.new_empty(B, P, dtype=torch.int32), x.new_empty(B, P, dtype=torch.int32))
+
+
+@torch.library.custom_op("fs2::path_stats", mutates_args=())
+def path_stats(a: Tensor, b: Tensor, path_i: Tensor, path_j: Tensor, K: Tensor) -> Tuple[Tensor, Tensor]:
+    return tuple(ops.path_stats(a, b, path_i, path_j, K))
+
+
+@path_stats.register_fake
+def _path_stats_fake(a, b, path_i, path_j, K):
+    B, _, Ch = a.shape
+    return a.new_empty(B, Ch, 4, dtype=torch.int64), a.new_empty(B, Ch, 2, dtype=torch.float64)
+
+
+# the objective evaluation (include/fs2hip_eval.h), on its own as OPS_ALIGN is
+OPS_EVAL = ("mel_cepstrum", "pair_dist", "dtw", "path_stats")

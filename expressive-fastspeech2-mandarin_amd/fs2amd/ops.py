@@ -2386,3 +2386,154 @@ def forward_sum_bwd(logp, mel_lens, text_lens, alpha, nll, grad_out=None, *, bla
                                      float(blank_logprob), _ptr(alpha), _ptr(nll), _ptr(go), _ptr(out), _stream(logp)),
             "fs2_forward_sum_bwd")
     return out
+
+
+DtwOut = collections.namedtuple("DtwOut", "total K path_i path_j")
+PathStatsOut = collections.namedtuple("PathStatsOut", "counts sums")
+_DTW_BITMAP = {"auto": L.DTW_AUTO, "lds": L.DTW_LDS, "global": L.DTW_GLOBAL}
+
+
+def _eval_rows(x, lens, what, name):
+    """(dtype code, batch stride, row stride, device lens, host lens or None) of a feature tensor
+    x [B, T_max, D] of include/fs2hip_eval.h: float32 or float64, unit stride along D, rows and
+    utterances that do not overlap. Host lengths are checked against [0, T_max]."""
+    _gpu(x)
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.float64) or min(x.shape) < 1:
+        raise ValueError(f"fs2amd: {what} takes {name} as a float32 or float64 [B >= 1, T_max >= 1, D >= 1] tensor")
+    B, T_max, D = x.shape
+    if D > 1 and x.stride(2) != 1:
+        raise ValueError(f"fs2amd: {what} needs unit stride along the last axis of {name}")
+    rs = x.stride(1) if T_max > 1 else D
+    bs = x.stride(0) if B > 1 else T_max * rs
+    if rs < D or bs < (T_max - 1) * rs + D:
+        raise ValueError(f"fs2amd: {what}: rows or utterances of {name} overlap (row stride {rs}, batch stride {bs})")
+    dev, host = _lengths_arg(lens, B, x.device, f"{name}_lens")
+    _gpu(dev)
+    if host is not None and (int(host.min()) < 0 or int(host.max()) > T_max):
+        raise ValueError(f"fs2amd: {name}_lens must lie in [0, {T_max}]")
+    return (L.FS2_F64 if x.dtype == torch.float64 else L.FS2_F32), bs, rs, dev, host
+
+
+def _eval_pair(x, x_lens, y, y_lens, what):
+    cx, xbs, xrs, xl, xh = _eval_rows(x, x_lens, what, "x")
+    cy, ybs, yrs, yl, yh = _eval_rows(y, y_lens, what, "y")
+    if cx != cy or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2] or x.device != y.device:
+        raise ValueError(f"fs2amd: {what} takes x [B, Tx_max, D] and y [B, Ty_max, D] of one dtype, batch size, D and "
+                         f"device, got {tuple(x.shape)} {x.dtype} and {tuple(y.shape)} {y.dtype}")
+    return cx, (xbs, xrs, ybs, yrs), (xl, yl), (xh, yh)
+
+
+def mel_cepstrum(mel, lens=None, *, basis, out=None):
+    """fs2_mel_cepstrum (include/fs2hip_eval.h): log-mel frames mel f32 or f64 [B, T_max, M] (unit
+    stride along M, any row and batch stride), ragged through lens [B], times the table basis f64
+    [C, M] -> cepstra f64 [B, T_max, C], c[t, q] = sum_m mel[t, m] * basis[q, m] summed in index order
+    from zero (bit for bit a numpy restatement in that order); rows t >= T_b are zeros."""
+    code, bs, rs, lens_dev, _ = _eval_rows(mel, lens, "mel_cepstrum", "mel")
+    B, T_max, M = mel.shape
+    _gpu(basis)
+    if basis.dim() != 2 or basis.shape[1] != M or basis.shape[0] < 1 or basis.dtype != torch.float64 \
+            or not basis.is_contiguous() or basis.device != mel.device:
+        raise ValueError(f"fs2amd: mel_cepstrum takes basis as a contiguous float64 [C >= 1, {M}] tensor on {mel.device}")
+    C = basis.shape[0]
+    if B * T_max * C > (1 << 31) - 1:
+        raise ValueError(f"fs2amd: mel_cepstrum writes at most 2^31 - 1 values, got {B} x {T_max} x {C}")
+    if out is None:
+        out = torch.empty(B, T_max, C, device=mel.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, T_max, C) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"fs2amd: out must be a contiguous float64 [{B}, {T_max}, {C}] device tensor")
+    L.check(_lib.fs2_mel_cepstrum(_ptr(mel), code, bs, rs, _ptr(lens_dev), _ptr(basis), B, T_max, M, C, _ptr(out),
+                                  _stream(mel)), "fs2_mel_cepstrum")
+    return out
+
+
+def pair_dist(x, x_lens, y, y_lens, *, squared=False, out=None):
+    """fs2_pair_dist: c[b, i, j] = sqrt(sum_d (x[b, i, d] - y[b, j, d])^2), the sum in float64 in index
+    order from zero, for x [B, Tx_max, D] and y [B, Ty_max, D] (f32 or f64, one dtype) -> f64
+    [B, Tx_max, Ty_max], zeros outside [Tx_b, Ty_b]. The cost ``dtw`` uses, from the same device code.
+    squared=True leaves the square root out: the sums themselves, determined bit for bit."""
+    code, strides, (xl, yl), _ = _eval_pair(x, x_lens, y, y_lens, "pair_dist")
+    B, Tx_max, D = x.shape
+    Ty_max = y.shape[1]
+    if B * Tx_max * Ty_max > (1 << 31) - 1:
+        raise ValueError(f"fs2amd: pair_dist writes at most 2^31 - 1 values, got {B} x {Tx_max} x {Ty_max}")
+    if out is None:
+        out = torch.empty(B, Tx_max, Ty_max, device=x.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, Tx_max, Ty_max) or not out.is_contiguous() \
+            or not out.is_cuda:
+        raise ValueError(f"fs2amd: out must be a contiguous float64 [{B}, {Tx_max}, {Ty_max}] device tensor")
+    L.check(_lib.fs2_pair_dist(_ptr(x), _ptr(y), code, *strides, _ptr(xl), _ptr(yl), B, Tx_max, Ty_max, D,
+                               int(bool(squared)), _ptr(out), _stream(x)), "fs2_pair_dist")
+    return out
+
+
+def dtw(x, x_lens, y, y_lens, *, bitmap="auto", out=None):
+    """fs2_dtw (include/fs2hip_eval.h): dynamic time warping of x [B, Tx_max, D] onto y [B, Ty_max, D]
+    (f32 or f64, one dtype; ragged through x_lens, y_lens) under the cost of ``pair_dist`` ->
+    DtwOut(total f64 [B], the accumulated cost at the end cell; K int32 [B], the cells on the path;
+    path_i, path_j int32 [B, Tx_max + Ty_max - 1], the path from (0, 0) on, -1 from K_b on). Steps:
+    diagonal if it is no dearer than both others, else up (i - 1) if no dearer than left (j - 1); given
+    the costs every output is determined bit for bit. With host lengths a zero length raises ValueError;
+    with device lengths such an utterance gets +inf, 0 and -1. bitmap: where the 2-bit steps live,
+    "auto" (LDS where they fit), "lds" or "global": the same bits out. out: (total, K, path_i, path_j)
+    buffers to write into."""
+    code, strides, (xl, yl), hosts = _eval_pair(x, x_lens, y, y_lens, "dtw")
+    B, Tx_max, D = x.shape
+    Ty_max = y.shape[1]
+    for host, given in zip(hosts, (x_lens, y_lens)):
+        if given is not None and host is not None and int(host.min()) < 1:
+            raise ValueError("fs2amd: dtw needs at least one frame on either side of every utterance")
+    if bitmap not in _DTW_BITMAP:
+        raise ValueError(f"fs2amd: dtw bitmap must be one of {sorted(_DTW_BITMAP)}, got {bitmap!r}")
+    rows = int(_lib.fs2_dtw_lds_bytes(Tx_max, Ty_max, 0))
+    if rows > L.DTW_LDS_BYTES:
+        raise ValueError(f"fs2amd: dtw keeps three anti-diagonals of {Tx_max} frames in {rows} bytes of LDS; the "
+                         f"limit is {L.DTW_LDS_BYTES}")
+    need = int(_lib.fs2_dtw_lds_bytes(Tx_max, Ty_max, 1))
+    if bitmap == "lds" and need > L.DTW_LDS_BYTES:
+        raise ValueError(f"fs2amd: dtw with the bitmap in LDS needs {need} bytes for {Tx_max} x {Ty_max} frames; the "
+                         f"limit is {L.DTW_LDS_BYTES}")
+    in_global = bitmap == "global" or need > L.DTW_LDS_BYTES
+    ws, ws_bytes = None, 0
+    if in_global:
+        ws_bytes = int(_lib.fs2_dtw_ws_bytes(B, Tx_max, Ty_max))
+        ws = torch.empty(ws_bytes // 8, device=x.device, dtype=torch.int64)
+    P = Tx_max + Ty_max - 1
+    if out is None:
+        total = torch.empty(B, device=x.device, dtype=torch.float64)
+        K = torch.empty(B, device=x.device, dtype=torch.int32)
+        path_i = torch.empty(B, P, device=x.device, dtype=torch.int32)
+        path_j = torch.empty(B, P, device=x.device, dtype=torch.int32)
+    else:
+        total, K, path_i, path_j = out
+        for t, dt, shape in ((total, torch.float64, (B,)), (K, torch.int32, (B,)), (path_i, torch.int32, (B, P)),
+                             (path_j, torch.int32, (B, P))):
+            if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"fs2amd: dtw out buffers must be contiguous {dt} {list(shape)}")
+        _gpu(total, K, path_i, path_j)
+    L.check(_lib.fs2_dtw(_ptr(x), _ptr(y), code, *strides, _ptr(xl), _ptr(yl), B, Tx_max, Ty_max, D,
+                         _DTW_BITMAP[bitmap], _ptr(ws), ws_bytes, _ptr(total), _ptr(K), _ptr(path_i), _ptr(path_j),
+                         _stream(x)), "fs2_dtw")
+    return DtwOut(total, K, path_i, path_j)
+
+
+def path_stats(a, b, path_i, path_j, K):
+    """fs2_path_stats: tracks a f64 [B, Tx_max, Ch] and b f64 [B, Ty_max, Ch] (NaN = absent) read along
+    the path of ``dtw`` (path_i, path_j int32 [B, Tx_max + Ty_max - 1], K int32 [B]) ->
+    PathStatsOut(counts int64 [B, Ch, 4] = n_both, n_a_only, n_b_only, n_none; sums f64 [B, Ch, 2] =
+    sum d, sum d^2 over the both-present pairs, d = a[i_k] - b[j_k], in path order from zero)."""
+    _gpu(a, b, path_i, path_j, K)
+    if a.dim() != 3 or b.dim() != 3 or a.dtype != torch.float64 or b.dtype != torch.float64 or min(a.shape) < 1 \
+            or min(b.shape) < 1 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        raise ValueError("fs2amd: path_stats takes a [B, Tx_max, Ch] and b [B, Ty_max, Ch] as float64 tensors")
+    B, Tx_max, Ch = a.shape
+    Ty_max = b.shape[1]
+    P = Tx_max + Ty_max - 1
+    for t, shape, name in ((path_i, (B, P), "path_i"), (path_j, (B, P), "path_j"), (K, (B,), "K")):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape:
+            raise ValueError(f"fs2amd: path_stats takes {name} as an int32 {list(shape)} tensor")
+    a, b, path_i, path_j, K = (t.contiguous() for t in (a, b, path_i, path_j, K))
+    counts = torch.empty(B, Ch, 4, device=a.device, dtype=torch.int64)
+    sums = torch.empty(B, Ch, 2, device=a.device, dtype=torch.float64)
+    L.check(_lib.fs2_path_stats(_ptr(a), _ptr(b), _ptr(path_i), _ptr(path_j), _ptr(K), B, Tx_max, Ty_max, Ch,
+                                _ptr(counts), _ptr(sums), _stream(a)), "fs2_path_stats")
+    return PathStatsOut(counts, sums)
