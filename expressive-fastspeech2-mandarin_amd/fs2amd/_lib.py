@@ -29,6 +29,9 @@ ALIGN_SIZE_CAP = 1 << 24  # csrc/align_sizes.h: FS2_AL_SIZE_CAP
 DTW_LDS_BYTES, DTW_LDS_SMALL = 163840, 32768
 DTW_AUTO, DTW_LDS, DTW_GLOBAL = 0, 1, 2
 EVAL_SIZE_CAP = 1 << 24  # csrc/eval_sizes.h: FS2_EV_SIZE_CAP
+# include/fs2hip_f0_track.h: FS2_F0_TRACK_THR, _CAP_MAX, _BINS_MAX, _STEP_MAX, _TB, _LDS_BYTES
+F0_TRACK_THR, F0_TRACK_CAP_MAX, F0_TRACK_BINS_MAX, F0_TRACK_STEP_MAX, F0_TRACK_TB = 100, 101, 256, 63, 64
+F0_TRACK_LDS_BYTES = 65536
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -448,6 +451,42 @@ def dtw_form(Tx_max, Ty_max, bitmap=DTW_AUTO):
     return FS2_OK, DTW_GLOBAL if bitmap == DTW_GLOBAL or not fits else DTW_LDS
 
 
+# include/fs2hip_f0_track.h: the cmnd table of fs2_f0_yin -> an F0 path through the utterance (Viterbi)
+SIGNATURES_F0_TRACK = {
+    "fs2_f0_track_lds_bytes": (_i64, [_i, _i]),
+    "fs2_f0_track_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "fs2_f0_track": (_i, [_p, _p, _i, _i, _i, _d, _i, _i, _d, _d, _p, _p, _p, _p, _p, _i, _p, _p, _i, _d, _d, _p, _i64,
+                          _p, _p, _p, _p]),
+}
+
+
+def f0_track_cap(tau_min, tau_max):
+    """ft_cap of csrc/f0_track_sizes.h: the candidates of one frame that can survive."""
+    return min((tau_max - tau_min + 1) // 2, F0_TRACK_CAP_MAX)
+
+
+def f0_track_workspace_bytes(B, F_max, tau_min, tau_max, n_bins):
+    """The Python mirror of csrc/f0_track_sizes.h (f0_track_sizes): the frame heads, the three candidate
+    lists and the predecessor bytes, each rounded up to 8 bytes. 0 for a size below 1, 2^63 - 1 where
+    it does not fit."""
+    if B < 1 or F_max < 1 or n_bins < 1 or tau_min < 2 or tau_min >= tau_max:
+        return 0
+    frames = B * F_max
+    ents = frames * f0_track_cap(tau_min, tau_max)
+    r8 = lambda a: (a + 7) // 8 * 8  # noqa: E731
+    n = r8(8 * frames) + 16 * ents + r8(4 * ents) + r8(frames * 2 * n_bins)
+    return min(n, (1 << 63) - 1)
+
+
+def f0_track_lds_bytes(n_bins, max_step):
+    """f0_track_lds_bytes of the same header."""
+    if n_bins < 1 or max_step < 0:
+        return 0
+    if max(n_bins, max_step) > 1 << 24:
+        return (1 << 63) - 1
+    return 8 * (4 * (n_bins + 2 * max_step) + 2 * n_bins) + F0_TRACK_TB * 2 * n_bins + 8
+
+
 def f0_dp_ulps(W, tau):
     """FS2_F0_DP_ULPS of the same header: the bound on dp's relative error, in units of 2^-53."""
     return 2 * W + tau + 6
@@ -473,8 +512,9 @@ HEADER_F0 = os.path.join(os.path.dirname(HEADER), "fs2hip_f0.h")
 HEADER_RESAMPLE = os.path.join(os.path.dirname(HEADER), "fs2hip_resample.h")
 HEADER_ALIGN = os.path.join(os.path.dirname(HEADER), "fs2hip_align.h")
 HEADER_EVAL = os.path.join(os.path.dirname(HEADER), "fs2hip_eval.h")
+HEADER_F0_TRACK = os.path.join(os.path.dirname(HEADER), "fs2hip_f0_track.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
-                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h")
+                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -521,7 +561,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
-            list(SIGNATURES_EVAL.items()):
+            list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -52,6 +52,9 @@ trace through it with ``fullgraph=True`` instead of breaking the graph at a ctyp
   [C, M] (include/fs2hip_eval.h): f64 [B, T_max, C], summed in index order, zeros past every T_b.
 * ``fs2::pair_dist(x, x_lens, y, y_lens) -> cost`` — Euclidean distances between the frames of
   x [B, Tx_max, D] and y [B, Ty_max, D] in float64: f64 [B, Tx_max, Ty_max], zeros outside [Tx_b, Ty_b].
+* ``fs2::f0_track(cmnd, lens, sampling_rate, hop, f0_floor, f0_ceil, bins_per_semitone, max_step, switch_prob)
+  -> (f0, state, score)`` — an F0 path through the utterance over the table ``fs2::f0_yin`` returns
+  (include/fs2hip_f0_track.h): pYIN-style candidates and a Viterbi recursion over pitch bin and voicing.
 * ``fs2::dtw(x, x_lens, y, y_lens, bitmap) -> (total, K, path_i, path_j)`` — dynamic time warping under
   that cost: total f64 [B], K int32 [B], path_i / path_j int32 [B, Tx_max + Ty_max - 1] (-1 from K_b on);
   bitmap 0 / 1 / 2 = auto / LDS / global, the same bits out.
@@ -283,6 +286,24 @@ def _f0_yin_fake(wav, lens, sampling_rate, hop, win, f0_floor, f0_ceil, threshol
 
 # the F0 estimator (include/fs2hip_f0.h), on its own as OPS_PREP is
 OPS_F0 = ("f0_yin",)
+
+
+@torch.library.custom_op("fs2::f0_track", mutates_args=())
+def f0_track(cmnd: Tensor, lens: Optional[Tensor], sampling_rate: float, hop: int, f0_floor: float, f0_ceil: float,
+             bins_per_semitone: int, max_step: int, switch_prob: float) -> Tuple[Tensor, Tensor, Tensor]:
+    return tuple(ops.f0_track(cmnd, lens, sampling_rate=sampling_rate, hop_length=hop, f0_floor=f0_floor, f0_ceil=f0_ceil,
+                              bins_per_semitone=bins_per_semitone, max_step=max_step, switch_prob=switch_prob))
+
+
+@f0_track.register_fake
+def _f0_track_fake(cmnd, lens, sampling_rate, hop, f0_floor, f0_ceil, bins_per_semitone, max_step, switch_prob):
+    B, F_max = cmnd.shape[0], cmnd.shape[1]
+    return (cmnd.new_empty(B, F_max, dtype=torch.float64), cmnd.new_empty(B, F_max, dtype=torch.int32),
+            cmnd.new_empty(B, dtype=torch.float64))
+
+
+# the F0 tracker over that estimator's table (include/fs2hip_f0_track.h)
+OPS_F0_TRACK = ("f0_track",)
 
 
 @torch.library.custom_op("fs2::resample", mutates_args=())

@@ -2161,6 +2161,60 @@ def f0_yin(wav, lens=None, *, sampling_rate, hop_length, win_length=1024, f0_flo
     return F0Out(f0, tau, cmnd)
 
 
+F0TrackOut = collections.namedtuple("F0TrackOut", "f0 state score")
+
+
+def f0_track(cmnd, lens=None, *, sampling_rate, hop_length, f0_floor=71.0, f0_ceil=800.0, bins_per_semitone=5,
+             max_step=12, switch_prob=0.01, tables=None, want_score=True, workspace=None, out=None):
+    """fs2_f0_track (include/fs2hip_f0_track.h): cmnd f64 [B, F_max, tau_max + 1] contiguous, the table
+    ``f0_yin(..., want_cmnd=True)`` returns for the same sampling_rate / f0_floor / f0_ceil, and lens
+    [B] in samples as ``f0_yin`` takes them -> F0TrackOut(f0 f64 [B, F_max], 0 = unvoiced and 0 past
+    lens // hop + 1; state int32 [B, F_max], the path's pitch bin or -1; score f64 [B], the path's
+    log-probability, None unless want_score). pYIN-style tracking over this project's own table: every
+    trough a candidate, a prior over thresholds, Viterbi over pitch bin and voicing; not
+    librosa.pyin's values nor WORLD's. tables: a ``fs2amd.f0.F0TrackTables`` (default: the cached one
+    of the parameters). workspace: a contiguous uint8 tensor of at least
+    fs2_f0_track_workspace_bytes; out: (f0, state, score or None) buffers to write into."""
+    from .f0 import f0_track_tables
+
+    _gpu(cmnd)
+    tau_min, tau_max = f0_lags(sampling_rate, f0_floor, f0_ceil)
+    hop = int(hop_length)
+    if hop < 1 or tau_min < 2 or tau_min >= tau_max:
+        raise ValueError(f"fs2amd: f0_track needs hop >= 1 and 2 <= tau_min < tau_max, got lags {tau_min}..{tau_max}")
+    if cmnd.dim() != 3 or cmnd.dtype != torch.float64 or not cmnd.is_contiguous() or cmnd.shape[2] != tau_max + 1 \
+            or cmnd.shape[1] < 1:
+        raise ValueError(f"fs2amd: cmnd must be a contiguous float64 [B, F_max >= 1, {tau_max + 1}] tensor")
+    B, F_max = cmnd.shape[0], cmnd.shape[1]
+    tb = f0_track_tables(sampling_rate, f0_floor, f0_ceil, bins_per_semitone, max_step, switch_prob) if tables is None \
+        else tables
+    N, K = int(tb.n_bins), int(tb.max_step)
+    if N > L.F0_TRACK_BINS_MAX or K > L.F0_TRACK_STEP_MAX or int(_lib.fs2_f0_track_lds_bytes(N, K)) > L.F0_TRACK_LDS_BYTES:
+        raise ValueError(f"fs2amd: f0_track holds at most {L.F0_TRACK_BINS_MAX} pitch bins and steps of "
+                         f"{L.F0_TRACK_STEP_MAX}, got {N} and {K}")
+    dev = cmnd.device
+    lens_dev, _ = _lengths_arg(lens, B, dev, "lens")
+    _gpu(lens_dev)
+    need = int(_lib.fs2_f0_track_workspace_bytes(B, F_max, tau_min, tau_max, N))
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError(f"fs2amd: f0_track needs a contiguous uint8 workspace of {need} bytes")
+    if out is None:
+        f0 = torch.empty(B, F_max, device=dev, dtype=torch.float64)
+        state = torch.empty(B, F_max, device=dev, dtype=torch.int32)
+        score = torch.empty(B, device=dev, dtype=torch.float64) if want_score else None
+    else:
+        f0, state, score = out
+    t = tb.to(dev)
+    L.check(_lib.fs2_f0_track(_ptr(cmnd), _ptr(lens_dev), B, F_max, hop, float(sampling_rate), tau_min, tau_max,
+                              float(f0_floor), float(f0_ceil), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), _ptr(t[4]),
+                              N, _ptr(t[5]), _ptr(t[6]), K, float(tb.log_floor), float(tb.log_init), _ptr(workspace),
+                              workspace.numel(), _ptr(f0), _ptr(state), _ptr(score), _stream(cmnd)), "fs2_f0_track")
+    return F0TrackOut(f0, state, score)
+
+
 ResampleOut = collections.namedtuple("ResampleOut", "y y32 peak out_lens")
 
 

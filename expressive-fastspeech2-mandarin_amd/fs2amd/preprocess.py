@@ -99,20 +99,37 @@ def pitch_targets(f0_list, durations, *, device=None, return_filled=False):
 F0_DEFAULTS = {"f0_floor": 71.0, "f0_ceil": 800.0, "threshold": 0.1, "win_length": 1024}
 
 
-def _f0_rows(wav_dev, lens, **kw):
-    """ops.f0_yin over an uploaded batch -> the float64 contours [lens[b] // hop + 1] on the host."""
+F0_METHODS = ("yin", "track")
+
+
+def _f0_rows(wav_dev, lens, method="yin", **kw):
+    """ops.f0_yin over an uploaded batch -> the float64 contours [lens[b] // hop + 1] on the host.
+    method "track": the same launch with its cmnd table kept on the device, then ops.f0_track over it."""
     from . import ops
 
-    f0 = ops.f0_yin(wav_dev, torch.from_numpy(np.asarray(lens, dtype=np.int64)), want_tau=False, **kw).f0.cpu().numpy()
+    if method not in F0_METHODS:
+        raise ValueError(f"fs2amd: the F0 method is one of {F0_METHODS}, got {method!r}")
+    lens_t = torch.from_numpy(np.asarray(lens, dtype=np.int64))
+    if method == "yin":
+        f0 = ops.f0_yin(wav_dev, lens_t, want_tau=False, **kw).f0
+    else:
+        lens_dev = lens_t.to(wav_dev.device)
+        cmnd = ops.f0_yin(wav_dev, lens_dev, want_tau=False, want_cmnd=True, **kw).cmnd
+        f0 = ops.f0_track(cmnd, lens_dev, sampling_rate=kw["sampling_rate"], hop_length=kw["hop_length"],
+                          f0_floor=kw["f0_floor"], f0_ceil=kw["f0_ceil"], want_score=False).f0
+    f0 = f0.cpu().numpy()
     return [f0[b, :int(n) // int(kw["hop_length"]) + 1].copy() for b, n in enumerate(lens)]
 
 
 def f0_contour(wavs, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.0, f0_ceil=800.0, threshold=0.1,
-               device=None):
+               method="yin", device=None):
     """F0 contours of a list of 1-D int16 / float32 waveforms: a list of float64 arrays of length
     len(w) // hop_length + 1, one value per hop at sample k * hop_length, 0 where unvoiced: the
     grid, length and range (71-800 Hz) of the reference's pyworld call, but YIN (include/fs2hip_f0.h),
-    so the values are not WORLD's. A batch with any float32 waveform is processed as float32."""
+    so the values are not WORLD's. A batch with any float32 waveform is processed as float32.
+    method "yin": every frame decided on its own against ``threshold``. method "track": one path
+    through the utterance over the same table (include/fs2hip_f0_track.h, pYIN-style; ``threshold``
+    plays no part): fewer octave errors and dropped frames, other values again."""
     dev = _device(device)
     wavs = [np.asarray(w) for w in wavs]
     if any(w.ndim != 1 or w.dtype not in (np.int16, np.float32) for w in wavs):
@@ -121,7 +138,7 @@ def f0_contour(wavs, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.
         return []
     wav, lens = _pack(wavs, np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32)
     return _f0_rows(torch.from_numpy(wav).to(dev), lens, sampling_rate=sampling_rate, hop_length=hop_length,
-                    win_length=win_length, f0_floor=f0_floor, f0_ceil=f0_ceil, threshold=threshold)
+                    win_length=win_length, f0_floor=f0_floor, f0_ceil=f0_ceil, threshold=threshold, method=method)
 
 
 def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=None):
@@ -259,7 +276,7 @@ def _aligned_durations(batch, wav_dev, lens, stft, aligner):
 
 
 def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None, seed=1234, batch_size=16,
-                 emotions=None, aligner=None):
+                 emotions=None, aligner=None, f0_method="yin"):
     """Write a preprocessed corpus directory (preprocessor.py:116-224, :304-325) from utterances, an
     iterable of dicts with ``basename``, ``speaker``, ``phones`` (list of labels), ``raw_text``,
     ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
@@ -268,7 +285,8 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     An utterance without ``f0`` (or with None) gets its contour from ``ops.f0_yin`` over the batch
     already uploaded for the features, at the configuration's sampling rate and hop, with the
     defaults of ``f0_contour`` unless preprocess_config["preprocessing"]["pitch_extraction"] sets
-    ``f0_floor`` / ``f0_ceil`` / ``threshold`` / ``win_length``.
+    ``f0_floor`` / ``f0_ceil`` / ``threshold`` / ``win_length``. f0_method: "yin" or "track", as
+    ``f0_contour``'s method; a ``stats.json`` built with one goes with checkpoints trained on its targets.
     Three more optional keys: ``sampling_rate``, the rate of ``wav`` when it is raw audio: such an
     utterance goes through ``prepare_wavs`` first (resampled to the configuration's rate and
     peak-normalised to int16); ``start`` / ``end`` in seconds: the waveform (prepared or not) is cut
@@ -301,6 +319,8 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     for kind in ("mel", "pitch", "energy", "duration"):
         os.makedirs(os.path.join(out_dir, kind), exist_ok=True)
     f0_kw = dict(F0_DEFAULTS, **pp.get("pitch_extraction", {}))
+    if f0_method not in F0_METHODS:
+        raise ValueError(f"fs2amd: f0_method is one of {F0_METHODS}, got {f0_method!r}")
     sr = pp["audio"]["sampling_rate"]
     pitch_stats, energy_stats = CorpusStats(dev), CorpusStats(dev)
     speakers, lines, kept = {}, [], []  # kept: (speaker, basename, pitch, energy)
@@ -334,7 +354,7 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
         f0s = [u.get("f0") for u in batch]
         if any(f is None for f in f0s):
             est = _f0_rows(wav_dev, lens, sampling_rate=pp["audio"]["sampling_rate"],
-                           hop_length=pp["stft"]["hop_length"], **f0_kw)
+                           hop_length=pp["stft"]["hop_length"], method=f0_method, **f0_kw)
             f0s = [e if f is None else f for f, e in zip(f0s, est)]
         f0s = [np.asarray(f, dtype=np.float64) for f in f0s]
         ph = pitch_targets(f0s, durs, device=dev)
