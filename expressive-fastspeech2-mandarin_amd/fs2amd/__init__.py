@@ -11,10 +11,11 @@ from .loss import FastSpeech2Loss
 from .model import FastSpeech2, LengthRegulator
 from .optimizer import ScheduledOptim
 from .preprocess import (CorpusStats, build_corpus, f0_contour, get_alignment, normalize, pitch_targets,
-                         prepare_wavs, remove_outlier)
+                         prepare_wavs, remove_outlier, split_silence, trim_silence)
 
 __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator", "TacotronSTFT",
            "get_mel_from_wav", "extract_features", "mel_filterbank", "STFT", "griffin_lim", "inv_mel_spec",
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
            "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
-           "mas_durations", "fit_aligner", "mcd", "dtw", "mel_cepstrum", "f0_metrics", "evaluate"]
+           "mas_durations", "fit_aligner", "trim_silence", "split_silence", "mcd", "dtw", "mel_cepstrum", "f0_metrics",
+           "evaluate"]

@@ -32,6 +32,8 @@ EVAL_SIZE_CAP = 1 << 24  # csrc/eval_sizes.h: FS2_EV_SIZE_CAP
 # include/fs2hip_f0_track.h: FS2_F0_TRACK_THR, _CAP_MAX, _BINS_MAX, _STEP_MAX, _TB, _LDS_BYTES
 F0_TRACK_THR, F0_TRACK_CAP_MAX, F0_TRACK_BINS_MAX, F0_TRACK_STEP_MAX, F0_TRACK_TB = 100, 101, 256, 63, 64
 F0_TRACK_LDS_BYTES = 65536
+# include/fs2hip_vad.h: FS2_VAD_SUMS_BYTES, _AREA_BYTES, _TILE_FRAMES, _CHUNK_FRAMES, _B_MAX
+VAD_SUMS_BYTES, VAD_AREA_BYTES, VAD_TILE_FRAMES, VAD_CHUNK_FRAMES, VAD_B_MAX = 32768, 32768, 192, 256, 65535
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -460,6 +462,66 @@ SIGNATURES_F0_TRACK = {
 }
 
 
+# include/fs2hip_vad.h: frame power, activity mask / intervals / trim, the ragged cut
+SIGNATURES_VAD = {
+    "fs2_vad_frames": (_i64, [_i64, _i64]),
+    "fs2_vad_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "fs2_vad_lds_bytes": (_i64, [_i64, _i64]),
+    "fs2_vad_power": (_i, [_p, _i, _i64, _p, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
+    "fs2_vad_intervals": (_i, [_p, _p, _p, _i, _i, _i, _d, _d, _i, _i64, _i, _i, _p, _p, _p, _p, _p]),
+    "fs2_vad_cut": (_i, [_p, _i, _i64, _p, _i, _i, _i, _p, _p, _p]),
+}
+
+
+def vad_frames(n, hop):
+    """vad_frames of csrc/vad_sizes.h: 0 for n < 1, else 1 + n // hop."""
+    return 0 if n < 1 else 1 + n // hop
+
+
+def vad_tile_frames(frame_length, hop):
+    """vad_tile_frames: frames per workgroup of fs2_vad_power, 0 where one frame's block sums do not fit."""
+    import math
+
+    g = math.gcd(frame_length, hop)
+    q, h = frame_length // g, hop // g
+    if q > VAD_SUMS_BYTES // 8:
+        return 0
+    return min((VAD_SUMS_BYTES // 8 - q) // h + 1, VAD_TILE_FRAMES)
+
+
+def vad_workspace_bytes(B, F_max, frame_length, hop):
+    """vad_workspace_bytes: one f64 maximum per tile and row. 0 for a size below 1, hop > frame_length or
+    a geometry without a tile, 2^63 - 1 where it does not fit."""
+    if B < 1 or F_max < 1 or frame_length < 1 or hop < 1 or hop > frame_length:
+        return 0
+    G = vad_tile_frames(frame_length, hop)
+    return min(8 * B * ((F_max + G - 1) // G), (1 << 63) - 1) if G >= 1 else 0
+
+
+def vad_lds_bytes(frame_length, hop):
+    """vad_lds_bytes: one frame's block sums as f64 and one block of f32 samples at its padded stride."""
+    import math
+
+    if frame_length < 1 or hop < 1 or hop > frame_length:
+        return 0
+    g = math.gcd(frame_length, hop)
+    return 8 * (frame_length // g) + 4 * (g | 1)
+
+
+def vad_status(B, n_max, frame_length, hop):
+    """vad_check: the status fs2_vad_power gives these sizes."""
+    import math
+
+    if B < 1 or n_max < 1 or frame_length < 1 or hop < 1 or hop > frame_length:
+        return FS2_EINVAL
+    g = math.gcd(frame_length, hop)
+    F = vad_frames(n_max, hop)
+    if B > VAD_B_MAX or 8 * (frame_length // g) > VAD_SUMS_BYTES or 4 * (g | 1) > VAD_AREA_BYTES \
+            or F > 2 ** 31 - 1 or B * F > (2 ** 31 - 1) // 8:
+        return FS2_EUNSUPPORTED
+    return FS2_OK
+
+
 def f0_track_cap(tau_min, tau_max):
     """ft_cap of csrc/f0_track_sizes.h: the candidates of one frame that can survive."""
     return min((tau_max - tau_min + 1) // 2, F0_TRACK_CAP_MAX)
@@ -513,8 +575,9 @@ HEADER_RESAMPLE = os.path.join(os.path.dirname(HEADER), "fs2hip_resample.h")
 HEADER_ALIGN = os.path.join(os.path.dirname(HEADER), "fs2hip_align.h")
 HEADER_EVAL = os.path.join(os.path.dirname(HEADER), "fs2hip_eval.h")
 HEADER_F0_TRACK = os.path.join(os.path.dirname(HEADER), "fs2hip_f0_track.h")
+HEADER_VAD = os.path.join(os.path.dirname(HEADER), "fs2hip_vad.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
-                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h")
+                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -561,7 +624,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
-            list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()):
+            list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -2591,3 +2591,131 @@ def path_stats(a, b, path_i, path_j, K):
     L.check(_lib.fs2_path_stats(_ptr(a), _ptr(b), _ptr(path_i), _ptr(path_j), _ptr(K), B, Tx_max, Ty_max, Ch,
                                 _ptr(counts), _ptr(sums), _stream(a)), "fs2_path_stats")
     return PathStatsOut(counts, sums)
+
+
+def vad_frames(n, hop):
+    """fs2_vad_frames (include/fs2hip_vad.h): 0 for n < 1, else 1 + n // hop."""
+    n, hop = int(n), int(hop)
+    if hop < 1:
+        raise ValueError(f"fs2amd: hop_length must be at least 1, got {hop}")
+    return L.vad_frames(n, hop)
+
+
+def _wav_rows(wav, what):
+    if wav.dim() != 2 or wav.dtype not in (torch.int16, torch.float32) or wav.shape[1] < 1 or wav.stride(1) != 1:
+        raise ValueError(f"fs2amd: {what} needs an int16 or float32 [B, n_max >= 1] tensor with unit sample stride")
+    B, n_max = wav.shape
+    stride = wav.stride(0) if B > 1 else n_max
+    if stride < n_max:
+        raise ValueError(f"fs2amd: wav rows overlap (row stride {stride} < {n_max})")
+    return B, n_max, stride, L.FS2_I16 if wav.dtype == torch.int16 else L.FS2_F32
+
+
+def frame_power(wav, lens=None, *, frame_length, hop_length, out=None):
+    """fs2_vad_power (include/fs2hip_vad.h): wav int16 or float32 [B, n_max] (ragged through lens [B])
+    -> (P f64 [B, F_max], the mean square of every centred, zero-padded frame of frame_length samples
+    every hop_length, in the header's fixed pairwise order, 0 past the row's 1 + len // hop_length
+    frames; Pmax f64 [B], its row maximum; n_frames int64 [B]). out: (P, Pmax) buffers to write into."""
+    _gpu(wav)
+    B, n_max, stride, dtype = _wav_rows(wav, "frame_power")
+    fl, hop = int(frame_length), int(hop_length)
+    rc = L.vad_status(B, n_max, fl, hop)
+    if rc == L.FS2_EINVAL:
+        raise ValueError(f"fs2amd: frame_power needs 1 <= hop_length <= frame_length, got {hop}, {fl}")
+    if rc != L.FS2_OK:
+        raise ValueError(f"fs2amd: frame_power does not take these sizes (B {B}, n_max {n_max}, frame_length {fl}, "
+                         f"hop_length {hop}; include/fs2hip_vad.h states the limits)")
+    F_max = L.vad_frames(n_max, hop)
+    lens_dev, _ = _lengths_arg(lens, B, wav.device, "lens")
+    _gpu(lens_dev)
+    if out is None:
+        P = torch.empty(B, F_max, device=wav.device, dtype=torch.float64)
+        Pmax = torch.empty(B, device=wav.device, dtype=torch.float64)
+    else:
+        P, Pmax = out
+        for t, shape in ((P, (B, F_max)), (Pmax, (B,))):
+            if t is None or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"fs2amd: frame_power out buffers must be contiguous float64 {list(shape)} device tensors")
+    ws_bytes = int(_lib.fs2_vad_workspace_bytes(B, F_max, fl, hop))
+    ws = torch.empty(ws_bytes // 8, device=wav.device, dtype=torch.float64)
+    L.check(_lib.fs2_vad_power(_ptr(wav), dtype, stride, _ptr(lens_dev), B, n_max, fl, hop, _ptr(P), _ptr(Pmax),
+                               _ptr(ws), ws_bytes, _stream(wav)), "fs2_vad_power")
+    if lens_dev is None:
+        n_frames = torch.full((B,), F_max, device=wav.device, dtype=torch.int64)
+    else:
+        n = lens_dev.clamp(0, n_max)
+        n_frames = torch.where(n > 0, n // hop + 1, torch.zeros_like(n))
+    return P, Pmax, n_frames
+
+
+def activity_intervals(P, Pmax, lens, *, threshold, floor, hop_length, min_silence=1, margin=0, max_intervals=None,
+                       n_max=None, chunk_frames=0, out=None):
+    """fs2_vad_intervals (include/fs2hip_vad.h): P f64 [B, F_max] and Pmax f64 [B] of frame_power, lens [B]
+    in samples (None: n_max each) -> (active uint8 [B, F_max]: max(P, floor) > threshold * max(Pmax, floor),
+    with inactive runs shorter than min_silence between two active frames filled; count int32 [B], the
+    number of active runs; intervals int64 [B, max_intervals, 2], their [start, end) in samples, zero past
+    the first min(count, max_intervals); trim int64 [B, 2] = (first start - margin, last end + margin)
+    clamped to the row, (0, 0) without an active frame). max_intervals: None = (F_max + 1) // 2, which
+    always suffices. n_max: the samples per row the frames were computed for (None: the largest count
+    that gives F_max frames). chunk_frames: frames per step of the kernel's walk (0: the default; the
+    result does not depend on it). out: (active, count, intervals, trim) buffers to write into."""
+    _gpu(P, Pmax)
+    if P.dim() != 2 or P.dtype != torch.float64 or P.shape[1] < 1 or not P.is_contiguous():
+        raise ValueError("fs2amd: P must be a contiguous float64 [B, F_max >= 1] tensor")
+    B, F_max = P.shape
+    if Pmax.dtype != torch.float64 or Pmax.shape != (B,) or not Pmax.is_contiguous():
+        raise ValueError(f"fs2amd: Pmax must be a contiguous float64 [{B}] tensor")
+    hop = int(hop_length)
+    if hop < 1:
+        raise ValueError(f"fs2amd: hop_length must be at least 1, got {hop}")
+    if n_max is None:
+        n_max = (F_max - 1) * hop + hop - 1
+    n_max = int(n_max)
+    if n_max < 1 or L.vad_frames(n_max, hop) != F_max:
+        raise ValueError(f"fs2amd: P has {F_max} frames per row, which {n_max} samples at hop_length {hop} do not give")
+    if max_intervals is None:
+        max_intervals = (F_max + 1) // 2
+    max_intervals, min_silence, margin = int(max_intervals), int(min_silence), int(margin)
+    if min_silence < 1 or margin < 0 or max_intervals < 0:
+        raise ValueError("fs2amd: activity_intervals needs min_silence >= 1, margin >= 0 and max_intervals >= 0")
+    if not (float(threshold) >= 0.0 and float(floor) >= 0.0):
+        raise ValueError("fs2amd: threshold and floor are non-negative numbers")
+    lens_dev, _ = _lengths_arg(lens, B, P.device, "lens")
+    _gpu(lens_dev)
+    shapes = ((torch.uint8, (B, F_max)), (torch.int32, (B,)), (torch.int64, (B, max_intervals, 2)), (torch.int64, (B, 2)))
+    if out is None:
+        out = tuple(torch.empty(shape, device=P.device, dtype=dt) for dt, shape in shapes)
+    else:
+        for t, (dt, shape) in zip(out, shapes):
+            if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"fs2amd: activity_intervals out buffers must be contiguous {dt} {list(shape)} device tensors")
+    active, count, intervals, trim = out
+    L.check(_lib.fs2_vad_intervals(_ptr(P), _ptr(Pmax), _ptr(lens_dev), B, n_max, hop, float(threshold), float(floor),
+                                   min_silence, margin, max_intervals, int(chunk_frames), _ptr(active), _ptr(count),
+                                   _ptr(intervals) if max_intervals > 0 else None, _ptr(trim), _stream(P)),
+            "fs2_vad_intervals")
+    return active, count, intervals, trim
+
+
+def cut_rows(wav, start, end, *, out=None):
+    """fs2_vad_cut (include/fs2hip_vad.h): wav int16 or float32 [B, n_max], start / end int64 [B] in
+    samples (device tensors; clamped to 0 <= start <= end <= n_max) -> (rows [B, M_max] of wav's dtype
+    with rows[b, :end - start] = wav[b, start:end] and zeros behind, M_max = max(end - start), at least
+    1; out_lens int64 [B]). Reading M_max waits for the device unless out (the rows buffer, whose width
+    is then M_max) is given."""
+    _gpu(wav, start, end)
+    B, n_max, stride, dtype = _wav_rows(wav, "cut_rows")
+    for t, name in ((start, "start"), (end, "end")):
+        if t.dtype != torch.int64 or t.shape != (B,):
+            raise ValueError(f"fs2amd: {name} must be an int64 [{B}] tensor")
+    trim = torch.stack([start, end], dim=1).contiguous()
+    if out is None:
+        M_max = max(int((trim[:, 1].clamp(0, n_max) - trim[:, 0].clamp(0, n_max)).clamp(min=0).max().item()), 1)
+        out = torch.empty(B, M_max, device=wav.device, dtype=wav.dtype)
+    elif out.dim() != 2 or out.dtype != wav.dtype or out.shape[0] != B or out.shape[1] < 1 or not out.is_contiguous() \
+            or not out.is_cuda:
+        raise ValueError(f"fs2amd: out must be a contiguous {wav.dtype} [{B}, M_max >= 1] device tensor")
+    out_lens = torch.empty(B, device=wav.device, dtype=torch.int64)
+    L.check(_lib.fs2_vad_cut(_ptr(wav), dtype, stride, _ptr(trim), B, n_max, out.shape[1], _ptr(out), _ptr(out_lens),
+                             _stream(wav)), "fs2_vad_cut")
+    return out, out_lens

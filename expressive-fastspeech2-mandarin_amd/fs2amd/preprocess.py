@@ -4,6 +4,9 @@ reference's preprocessor/preprocessor.py does between feature extraction and ``s
 * ``get_alignment`` — :327-365 over ``(start, end, label)`` intervals (host code).
 * ``prepare_wavs`` — the prepare_align step before it (preprocessor/esd_chinese.py:145-147): raw audio
   at any rate to peak-normalised int16 at the configuration's (include/fs2hip_resample.h).
+* ``trim_silence`` / ``split_silence`` — the rule of librosa.effects.trim / split in this project's own
+  float64 arithmetic (include/fs2hip_vad.h): what stands in for the TextGrid's first and last phone
+  (:245-249) where there is no TextGrid.
 * ``f0_contour`` — the contour the reference takes from pyworld (:255-261), here from YIN on the GPU.
 * ``pitch_targets`` — :263-291: crop, interpolate over unvoiced frames, phoneme mean.
 * ``remove_outlier`` / ``CorpusStats`` — :367-375 and the ``StandardScaler.partial_fit`` calls of
@@ -141,7 +144,88 @@ def f0_contour(wavs, *, sampling_rate, hop_length, win_length=1024, f0_floor=71.
                     win_length=win_length, f0_floor=f0_floor, f0_ceil=f0_ceil, threshold=threshold, method=method)
 
 
-def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=None):
+def _vad_params(top_db, dtype):
+    """(threshold, floor) of include/fs2hip_vad.h for top_db and a waveform dtype: 10 ** (-top_db / 10)
+    and librosa's amin on amplitude, (1e-5 * full_scale) ** 2 with full_scale 32768 for int16, 1 for float32."""
+    return 10 ** (-float(top_db) / 10), (1e-5 * (32768.0 if dtype == np.int16 else 1.0)) ** 2
+
+
+def _vad_batch(wav_dev, lens, dtype, *, top_db, frame_length, hop_length, min_silence, margin):
+    """ops.frame_power + ops.activity_intervals over an uploaded batch: (count, intervals, trim) on the device."""
+    from . import ops
+
+    lens_dev = torch.from_numpy(np.asarray(lens, dtype=np.int64)).to(wav_dev.device)
+    P, Pmax, _ = ops.frame_power(wav_dev, lens_dev, frame_length=frame_length, hop_length=hop_length)
+    threshold, floor = _vad_params(top_db, dtype)
+    _, count, intervals, trim = ops.activity_intervals(P, Pmax, lens_dev, threshold=threshold, floor=floor,
+                                                       hop_length=hop_length, min_silence=min_silence, margin=margin,
+                                                       n_max=wav_dev.shape[1])
+    return count, intervals, trim
+
+
+def _wav_list(wavs):
+    wavs = [np.asarray(w) for w in wavs]
+    if any(w.ndim != 1 or w.dtype not in (np.int16, np.float32) for w in wavs):
+        raise ValueError("fs2amd: waveforms are 1-D int16 or float32 arrays")
+    return wavs
+
+
+def trim_silence(wavs, *, top_db=60.0, frame_length=2048, hop_length=512, min_silence=1, margin=0, device=None):
+    """Leading and trailing silence cut from a list of 1-D int16 / float32 waveforms by the rule of
+    librosa.effects.trim (the defaults are librosa's): a centred, zero-padded frame is active where its
+    power exceeds the utterance's largest frame power less top_db decibels; the waveform is cut to
+    [first active frame * hop_length - margin, (last active frame + 1) * hop_length + margin), clamped.
+    Returns (the trimmed arrays, int64 [B, 2] of (start, end)). It is librosa's rule in this project's
+    float64 arithmetic (include/fs2hip_vad.h), not librosa's bits. Every waveform is judged in its own
+    dtype: int16 against full scale 32768, float32 against 1.0; each dtype is one batch on the device.
+    min_silence > 1 also counts inner pauses shorter than that many frames as speech (which moves
+    nothing here; see ``split_silence``). A waveform without an active frame comes back empty."""
+    from . import ops
+
+    dev = _device(device)
+    wavs = _wav_list(wavs)
+    res, se = [None] * len(wavs), np.zeros((len(wavs), 2), dtype=np.int64)
+    for dtype in (np.int16, np.float32):
+        idx = [b for b, w in enumerate(wavs) if w.dtype == dtype]
+        if not idx:
+            continue
+        wav, lens = _pack([wavs[b] for b in idx], dtype)
+        wav_dev = torch.from_numpy(wav).to(dev)
+        _, _, trim = _vad_batch(wav_dev, lens, dtype, top_db=top_db, frame_length=frame_length, hop_length=hop_length,
+                                min_silence=min_silence, margin=margin)
+        rows, out_lens = ops.cut_rows(wav_dev, trim[:, 0].contiguous(), trim[:, 1].contiguous())
+        rows, out_lens, trim = rows.cpu().numpy(), out_lens.cpu().numpy(), trim.cpu().numpy()
+        for j, b in enumerate(idx):
+            res[b] = rows[j, :int(out_lens[j])].copy()
+            se[b] = trim[j]
+    return res, se
+
+
+def split_silence(wavs, *, top_db=60.0, frame_length=2048, hop_length=512, min_silence=1, device=None):
+    """The non-silent intervals of a list of 1-D int16 / float32 waveforms by the rule of
+    librosa.effects.split: a list of int64 [k_b, 2] arrays of [start, end) in samples, one row per maximal
+    run of active frames, [first frame * hop_length, min(len, (last frame + 1) * hop_length)).
+    min_silence: inner pauses shorter than that many frames do not split (1: librosa's behaviour).
+    Arithmetic and dtypes as ``trim_silence``."""
+    dev = _device(device)
+    wavs = _wav_list(wavs)
+    res = [None] * len(wavs)
+    for dtype in (np.int16, np.float32):
+        idx = [b for b, w in enumerate(wavs) if w.dtype == dtype]
+        if not idx:
+            continue
+        wav, lens = _pack([wavs[b] for b in idx], dtype)
+        count, intervals, _ = _vad_batch(torch.from_numpy(wav).to(dev), lens, dtype, top_db=top_db,
+                                         frame_length=frame_length, hop_length=hop_length, min_silence=min_silence,
+                                         margin=0)
+        count, intervals = count.cpu().numpy(), intervals.cpu().numpy()
+        for j, b in enumerate(idx):
+            res[b] = intervals[j, :int(count[j])].copy()
+    return res
+
+
+def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=None, trim_db=None,
+                 trim_frame_length=2048, trim_hop_length=512, trim_margin=0):
     """The reference's prepare_align arithmetic (preprocessor/esd_chinese.py:145-147) for a list of
     1-D int16 / float32 waveforms at the source rates ``rates`` (one per waveform, or one number for
     all): resampled to ``sampling_rate``, divided by the peak, scaled by max_wav_value and cut to
@@ -149,7 +233,10 @@ def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=No
     ops.resample + ops.peak_int16 pair per distinct source rate; a waveform already at
     ``sampling_rate`` is only peak-normalised, as the reference does to every file. The resampler is
     scipy.signal.resample_poly's (include/fs2hip_resample.h), not librosa's soxr_hq; a positive peak
-    comes out as 32767 where the reference's cast wraps. An all-zero waveform stays zero."""
+    comes out as 32767 where the reference's cast wraps. An all-zero waveform stays zero.
+    trim_db: None, or the top_db of ``trim_silence``: every group is then trimmed on the device after
+    the int16 pass and before the copy back (frames of trim_frame_length every trim_hop_length,
+    trim_margin samples kept on either side); on int16 rows every sum of the frame power is exact."""
     from . import ops
     from .audio import resample_ratio, resample_taps
 
@@ -172,9 +259,16 @@ def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=No
         wav, lens = _pack(group, np.int16 if all(w.dtype == np.int16 for w in group) else np.float32)
         taps = None if up == down == 1 else torch.from_numpy(resample_taps(up, down) * up).to(dev)
         o = ops.resample(torch.from_numpy(wav).to(dev), torch.from_numpy(lens), up=up, down=down, taps=taps, want_y=False)
-        q = ops.peak_int16(o.y32, o.peak, o.out_lens, max_wav_value=max_wav_value).cpu().numpy()
+        q = ops.peak_int16(o.y32, o.peak, o.out_lens, max_wav_value=max_wav_value)
+        out_lens = [ops.resample_out_len(int(n), up, down) for n in lens]
+        if trim_db is not None:
+            _, _, trim = _vad_batch(q, out_lens, np.int16, top_db=trim_db, frame_length=trim_frame_length,
+                                    hop_length=trim_hop_length, min_silence=1, margin=trim_margin)
+            q, cut_lens = ops.cut_rows(q, trim[:, 0].contiguous(), trim[:, 1].contiguous())
+            out_lens = cut_lens.cpu().tolist()
+        q = q.cpu().numpy()
         for j, b in enumerate(idx):
-            res[b] = q[j, :ops.resample_out_len(int(lens[j]), up, down)].copy()
+            res[b] = q[j, :out_lens[j]].copy()
     return res
 
 
@@ -276,7 +370,7 @@ def _aligned_durations(batch, wav_dev, lens, stft, aligner):
 
 
 def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None, seed=1234, batch_size=16,
-                 emotions=None, aligner=None, f0_method="yin"):
+                 emotions=None, aligner=None, f0_method="yin", trim_db=None, trim_margin=0):
     """Write a preprocessed corpus directory (preprocessor.py:116-224, :304-325) from utterances, an
     iterable of dicts with ``basename``, ``speaker``, ``phones`` (list of labels), ``raw_text``,
     ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
@@ -297,6 +391,13 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     then gets them from it. The mel of the prepared, cut waveform is computed first, over the batch
     already uploaded; the aligner's durations sum to its frame count. Utterances that bring
     ``durations`` go exactly as without an aligner, and a batch may mix both.
+    trim_db: None, or the top_db of ``trim_silence``: an utterance that brings neither ``start`` nor
+    ``end`` then has its leading and trailing silence cut (after ``prepare_wavs``, before anything else;
+    trim_margin samples kept on either side) with frames of the configuration's win_length every
+    hop_length, so that the cut lies on the mel grid. Its ``durations`` and ``f0``, if it brings any,
+    refer to the trimmed waveform: durations that sum to more frames than its mel has raise a ValueError
+    (everywhere else durations are expected to fit, as ``extract_features`` says). An utterance that
+    trims to nothing is dropped, as an all-silence TextGrid is.
 
     Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
     batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
@@ -339,10 +440,27 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
             start, end = u.get("start"), u.get("end")
             if start is not None or end is not None:
                 wavs[b] = wavs[b][None if start is None else int(sr * start):None if end is None else int(sr * end)]
+        if trim_db is not None:
+            free = [b for b, u in enumerate(batch) if u.get("start") is None and u.get("end") is None]
+            if free:
+                cut, _ = trim_silence([wavs[b] for b in free], top_db=trim_db, frame_length=pp["stft"]["win_length"],
+                                      hop_length=pp["stft"]["hop_length"], margin=trim_margin, device=dev)
+                for b, w in zip(free, cut):
+                    wavs[b] = w
+                    d = batch[b].get("durations")
+                    frames = 1 + len(w) // pp["stft"]["hop_length"]
+                    if d is not None and len(w) > 0 and int(np.sum(d)) > frames:
+                        raise ValueError(f"fs2amd: the durations of {batch[b]['basename']} sum to {int(np.sum(d))} frames; "
+                                         f"its trimmed waveform has {frames}")
         return wavs
 
     def flush(batch):
         wavs = raw_wavs(batch)
+        if trim_db is not None:  # trimmed to nothing: dropped, as preprocessor.py:245-246 drops start >= end
+            keep = [b for b, w in enumerate(wavs) if len(w) > 0]
+            batch, wavs = [batch[b] for b in keep], [wavs[b] for b in keep]
+            if not batch:
+                return
         wdtype = np.int16 if all(w.dtype == np.int16 for w in wavs) else np.float32
         wav, lens = _pack(wavs, wdtype)
         wav_dev = torch.from_numpy(wav).to(dev)

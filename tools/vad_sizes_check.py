@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Build tools/vad_sizes_check.cpp with the address and undefined-behaviour sanitizers, run it on the
+CPU (it compares csrc/vad_sizes.h with a 128-bit restatement of the same formulas over sizes up to
+INT32_MAX) and compare every line it prints with the Python mirror in fs2amd/_lib.py (the frame count,
+the tile, the workspace and LDS bytes and the status of fs2_vad_power). Exit status 0 and "ok" mean: the
+same numbers everywhere, and nothing reported by either sanitizer.
+
+    python tools/vad_sizes_check.py [--cxx g++]
+"""
+import argparse
+import importlib.util
+import math
+import os
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "expressive-fastspeech2-mandarin_amd")
+
+
+def mirror():
+    """fs2amd/_lib.py alone (it loads no library on import)."""
+    spec = importlib.util.spec_from_file_location("_fs2_lib_mirror", os.path.join(PKG, "fs2amd", "_lib.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def check(cxx, sanitize=True):
+    """Returns the number of lines compared; raises SystemExit on a mismatch or a sanitizer report.
+    sanitize=False builds the same program without the sanitizers (tests/test_vad_host.py: the comparison
+    alone, with no sanitizer runtime needed where the suite runs)."""
+    L = mirror()
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "vad_sizes_check")
+        san = "-fsanitize=address,undefined"
+        flags = [] if not sanitize else ["-Xarch_host", san] if os.path.basename(cxx).startswith("hipcc") else [san]
+        if sanitize:
+            flags.append("-fno-sanitize-recover=all")
+        subprocess.run([cxx, "-O1", "-g", "-std=c++17", *flags,
+                        f"-I{os.path.join(REPO, 'include')}", f"-I{os.path.join(PKG, 'csrc')}",
+                        os.path.join(REPO, "tools", "vad_sizes_check.cpp"), "-o", exe], check=True)
+        run = subprocess.run([exe], capture_output=True, text=True)
+    if run.returncode != 0 or run.stderr.strip():
+        sys.exit(f"the program failed (exit {run.returncode}):\n{run.stderr[-4000:]}")
+    n_lines = 0
+    for line in run.stdout.splitlines():
+        kind, *rest = line.split()
+        a = [int(v) for v in rest if v != "->"]
+        if kind == "F":
+            n, hop, F = a
+            want, got = (L.vad_frames(n, hop),), (F,)
+        elif kind == "G":
+            fl, hop, g, G, nb, lds, fits = a
+            Gm = L.vad_tile_frames(fl, hop)
+            gg = math.gcd(fl, hop)
+            want = (gg, Gm, (Gm - 1) * (hop // gg) + fl // gg if Gm >= 1 else 0, L.vad_lds_bytes(fl, hop),
+                    int(L.vad_status(1, 1, fl, hop) == L.FS2_OK))
+            got = (g, G, nb, lds, fits)
+        elif kind == "W":
+            B, F, fl, hop, ws = a
+            want, got = (L.vad_workspace_bytes(B, F, fl, hop),), (ws,)
+        elif kind == "C":
+            B, n, fl, hop, rc = a
+            want, got = (L.vad_status(B, n, fl, hop),), (rc,)
+        else:
+            fl, hop, lds = a
+            want, got = (L.vad_lds_bytes(fl, hop),), (lds,)
+        if want != got:
+            sys.exit(f"mismatch: {line}   Python: {want}")
+        n_lines += 1
+    return n_lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cxx", default=os.environ.get("CXX", "g++"))
+    args = ap.parse_args()
+    print(f"ok: {check(args.cxx)} lines agree with the Python mirror; the sanitizers reported nothing")
+
+
+if __name__ == "__main__":
+    main()
