@@ -4,6 +4,7 @@
     from fs2amd import TacotronSTFT         # drop-in for the reference audio/stft.py (mel / energy targets)
 """
 from .align import AlignmentEncoder, ForwardSumLoss, fit_aligner, mas_durations
+from .augment import augment_utterances, pitch_shift, time_stretch
 from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, griffin_lim, inv_mel_spec, mel_filterbank,
                     mel_to_wav, window_sumsquare)
 from .evaluate import dtw, evaluate, f0_metrics, mcd, mel_cepstrum
@@ -17,5 +18,5 @@ __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator"
            "get_mel_from_wav", "extract_features", "mel_filterbank", "STFT", "griffin_lim", "inv_mel_spec",
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
            "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
-           "mas_durations", "fit_aligner", "trim_silence", "split_silence", "mcd", "dtw", "mel_cepstrum", "f0_metrics",
-           "evaluate"]
+           "mas_durations", "fit_aligner", "trim_silence", "split_silence", "time_stretch", "pitch_shift",
+           "augment_utterances", "mcd", "dtw", "mel_cepstrum", "f0_metrics", "evaluate"]

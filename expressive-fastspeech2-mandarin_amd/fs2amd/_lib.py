@@ -34,6 +34,8 @@ F0_TRACK_THR, F0_TRACK_CAP_MAX, F0_TRACK_BINS_MAX, F0_TRACK_STEP_MAX, F0_TRACK_T
 F0_TRACK_LDS_BYTES = 65536
 # include/fs2hip_vad.h: FS2_VAD_SUMS_BYTES, _AREA_BYTES, _TILE_FRAMES, _CHUNK_FRAMES, _B_MAX
 VAD_SUMS_BYTES, VAD_AREA_BYTES, VAD_TILE_FRAMES, VAD_CHUNK_FRAMES, VAD_B_MAX = 32768, 32768, 192, 256, 65535
+# include/fs2hip_pvoc.h: FS2_PVOC_BLOCK, _J_CAP, _B_MAX
+PVOC_BLOCK, PVOC_J_CAP, PVOC_B_MAX = 64, 2 ** 31 - 1, 65535
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -213,6 +215,16 @@ class IstftDesc(ctypes.Structure):
         ("recomb", _p), ("recomb_row_stride", _i64), ("frames", _p), ("frames_host", _p), ("B", _i), ("T_in", _i),
         ("n_out_max", _i), ("n_fft", _i), ("hop", _i), ("win", _i), ("inv_packed", _p), ("wsum_table", _p),
         ("wav", _p), ("wav_row_stride", _i64), ("lens_out", _p),
+    ]
+
+
+class PvocDesc(ctypes.Structure):
+    """Mirror of ``fs2_pvoc_desc`` (include/fs2hip_pvoc.h)."""
+
+    _fields_ = [
+        ("spec", _p), ("spec_row_stride", _i64), ("frames", _p), ("frames_host", _p), ("rates", _p), ("rates_host", _p),
+        ("B", _i), ("NB", _i), ("T_max", _i), ("J_max", _i), ("recomb", _p), ("recomb_row_stride", _i64),
+        ("frames_out", _p),
     ]
 
 
@@ -473,6 +485,40 @@ SIGNATURES_VAD = {
 }
 
 
+# include/fs2hip_pvoc.h: the phase vocoder between fs2_stft and fs2_istft
+SIGNATURES_PVOC = {
+    "fs2_pvoc_frames": (_i64, [_i64, _d]),
+    "fs2_phase_vocoder": (_i, [ctypes.POINTER(PvocDesc), _p]),
+}
+
+
+def pvoc_frames(T, rate):
+    """pvoc_frames of csrc/pvoc_sizes.h: the number of j >= 0 with fl(j * rate) < T, saturated at
+    PVOC_J_CAP; 0 for T < 1 and for a rate that is not finite or is <= 0."""
+    import math
+
+    T, rate = int(T), float(rate)
+    if T < 1 or not rate > 0.0 or not math.isfinite(rate):
+        return 0
+    t = float(min(T, PVOC_J_CAP))
+    q = t / rate  # IEEE: an overflow gives inf
+    if not q < 2147483649.0:  # ceil(q) < 2147483650
+        return PVOC_J_CAP
+    j = math.ceil(q)
+    while j > 0 and not float(j - 1) * rate < t:
+        j -= 1
+    while float(j) * rate < t:
+        j += 1
+    return min(j, PVOC_J_CAP)
+
+
+def pvoc_status(B, NB, T_max, J_max, spec_row_stride, recomb_row_stride):
+    """pvoc_check: the status fs2_phase_vocoder gives these sizes."""
+    if B < 1 or NB < 1 or T_max < 1 or J_max < 1 or spec_row_stride < T_max or recomb_row_stride < J_max:
+        return FS2_EINVAL
+    return FS2_EUNSUPPORTED if B > PVOC_B_MAX else FS2_OK
+
+
 def vad_frames(n, hop):
     """vad_frames of csrc/vad_sizes.h: 0 for n < 1, else 1 + n // hop."""
     return 0 if n < 1 else 1 + n // hop
@@ -576,8 +622,10 @@ HEADER_ALIGN = os.path.join(os.path.dirname(HEADER), "fs2hip_align.h")
 HEADER_EVAL = os.path.join(os.path.dirname(HEADER), "fs2hip_eval.h")
 HEADER_F0_TRACK = os.path.join(os.path.dirname(HEADER), "fs2hip_f0_track.h")
 HEADER_VAD = os.path.join(os.path.dirname(HEADER), "fs2hip_vad.h")
+HEADER_PVOC = os.path.join(os.path.dirname(HEADER), "fs2hip_pvoc.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
-                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h")
+                 "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h",
+                 "fs2hip_pvoc.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -624,7 +672,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PROSODY.items()) + \
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
-            list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()):
+            list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()) + \
+            list(SIGNATURES_PVOC.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

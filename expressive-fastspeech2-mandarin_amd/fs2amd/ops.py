@@ -2719,3 +2719,72 @@ def cut_rows(wav, start, end, *, out=None):
     L.check(_lib.fs2_vad_cut(_ptr(wav), dtype, stride, _ptr(trim), B, n_max, out.shape[1], _ptr(out), _ptr(out_lens),
                              _stream(wav)), "fs2_vad_cut")
     return out, out_lens
+
+
+def pvoc_frames(T, rate):
+    """fs2_pvoc_frames (include/fs2hip_pvoc.h): the output frames of a row of T frames stretched by rate,
+    the number of j >= 0 with fl(j * rate) < T; 0 for a rate that is not finite or is <= 0."""
+    return L.pvoc_frames(T, rate)
+
+
+def phase_vocoder(spec, frames, rates, *, J_max=None, out=None):
+    """fs2_phase_vocoder (include/fs2hip_pvoc.h): spec f32 [B, 2 NB, T_max] (real rows, then imaginary
+    rows, as ops.stft gives it; unit frame stride, any row stride), frames per row (None = T_max each),
+    rates f64 [B] input frames per output frame -> (recomb f32 [B, 2 NB, J_max] in the layout ops.istft
+    reads, frames_out int64 [B] = the output frames of every row). Columns at or past a row's count are
+    0; a rate that is not finite or is <= 0 gives a row of zeros and a count of 0. The rule is
+    librosa.phase_vocoder's with the phase kept as a running product of unit rotors in float64; every
+    value is fixed bit for bit by the header and does not depend on the batch.
+
+    frames / rates: host data (a list, an array, a CPU tensor) is validated against J_max and copied; a
+    device tensor is passed as it is. J_max None: the largest count, at least 1 (frames and rates that
+    live on the device are read back for it, which waits for the device). A row whose count exceeds a
+    given J_max is cut there (its frames_out is still the true count) when the host cannot see that,
+    and refused when it can. out: (recomb, frames_out) buffers to write into; recomb may have a row
+    stride larger than J_max."""
+    _gpu(spec)
+    if spec.dim() != 3 or spec.shape[1] < 2 or spec.shape[1] % 2 or spec.shape[2] < 1:
+        raise ValueError("fs2amd: spec must be a float32 [B, 2 * NB, T_max >= 1] tensor")
+    B, rows, T_max = spec.shape
+    rs = _bin_major(spec, rows, "spec")
+    dev = spec.device
+    frames_dev, frames_host = _lengths_arg(frames, B, dev, "frames")
+    _gpu(frames_dev)
+    rates = torch.as_tensor(rates, dtype=torch.float64) if not torch.is_tensor(rates) else rates
+    if rates.shape != (B,):
+        raise ValueError(f"fs2amd: rates must have shape [{B}], got {tuple(rates.shape)}")
+    if rates.is_cuda:
+        rates_dev, rates_host = rates.to(torch.float64).contiguous(), None
+    else:
+        rates_host = rates.to(torch.float64).contiguous()
+        rates_dev = rates_host.to(dev)
+    _gpu(rates_dev)
+    if J_max is None:
+        r = rates_host if rates_host is not None else rates_dev.cpu()
+        f = [T_max] * B if frames is None else (frames_host if frames_host is not None else frames_dev.cpu()).tolist()
+        J_max = max([L.pvoc_frames(min(max(int(t), 0), T_max), float(x)) for t, x in zip(f, r.tolist())] + [1])
+    J_max = int(J_max)
+    if J_max < 1 or J_max > 2 ** 31 - 1:
+        raise ValueError(f"fs2amd: J_max must be in [1, 2^31 - 1], got {J_max}")
+    if out is None:
+        recomb = torch.empty(B, rows, J_max, device=dev, dtype=torch.float32)
+        frames_out = torch.empty(B, device=dev, dtype=torch.int64)
+    else:
+        recomb, frames_out = out
+        _gpu(recomb, frames_out)
+        if recomb.dim() != 3 or tuple(recomb.shape) != (B, rows, J_max):
+            raise ValueError(f"fs2amd: out recomb must be float32 [{B}, {rows}, {J_max}]")
+        if frames_out is not None and (frames_out.dtype != torch.int64 or frames_out.shape != (B,)
+                                       or not frames_out.is_contiguous()):
+            raise ValueError(f"fs2amd: out frames_out must be a contiguous int64 [{B}] tensor")
+    d = L.PvocDesc()
+    d.spec, d.spec_row_stride = spec.data_ptr(), rs
+    d.frames = frames_dev.data_ptr() if frames_dev is not None else None
+    d.frames_host = frames_host.data_ptr() if frames_host is not None else None
+    d.rates = rates_dev.data_ptr()
+    d.rates_host = rates_host.data_ptr() if rates_host is not None else None
+    d.B, d.NB, d.T_max, d.J_max = B, rows // 2, T_max, J_max
+    d.recomb, d.recomb_row_stride = recomb.data_ptr(), _bin_major(recomb, rows, "out recomb")
+    d.frames_out = frames_out.data_ptr() if frames_out is not None else None
+    L.check(_lib.fs2_phase_vocoder(ctypes.byref(d), _stream(spec)), "fs2_phase_vocoder")
+    return recomb, frames_out
