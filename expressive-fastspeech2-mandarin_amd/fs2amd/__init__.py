@@ -9,6 +9,7 @@ from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, grif
                     mel_to_wav, window_sumsquare)
 from .evaluate import dtw, evaluate, f0_metrics, mcd, mel_cepstrum
 from .loss import FastSpeech2Loss
+from .loudness import integrated_loudness, normalize_loudness
 from .model import FastSpeech2, LengthRegulator
 from .optimizer import ScheduledOptim
 from .preprocess import (CorpusStats, build_corpus, f0_contour, get_alignment, normalize, pitch_targets,
@@ -19,4 +20,5 @@ __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator"
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
            "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
            "mas_durations", "fit_aligner", "trim_silence", "split_silence", "time_stretch", "pitch_shift",
-           "augment_utterances", "mcd", "dtw", "mel_cepstrum", "f0_metrics", "evaluate"]
+           "augment_utterances", "integrated_loudness", "normalize_loudness", "mcd", "dtw", "mel_cepstrum",
+           "f0_metrics", "evaluate"]

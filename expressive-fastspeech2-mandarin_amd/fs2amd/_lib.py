@@ -36,6 +36,8 @@ F0_TRACK_LDS_BYTES = 65536
 VAD_SUMS_BYTES, VAD_AREA_BYTES, VAD_TILE_FRAMES, VAD_CHUNK_FRAMES, VAD_B_MAX = 32768, 32768, 192, 256, 65535
 # include/fs2hip_pvoc.h: FS2_PVOC_BLOCK, _J_CAP, _B_MAX
 PVOC_BLOCK, PVOC_J_CAP, PVOC_B_MAX = 64, 2 ** 31 - 1, 65535
+# include/fs2hip_iir.h: FS2_IIR_BLOCK, _CHUNK, _S_MAX, _TABLE_LEN, _B_MAX, FS2_LOUD_H_MAX
+IIR_BLOCK, IIR_CHUNK, IIR_S_MAX, IIR_TABLE_LEN, IIR_B_MAX, LOUD_H_MAX = 64, 16384, 8, 412, 65535, 32768
 FS2_OK, FS2_EINVAL, FS2_ELAUNCH, FS2_EUNSUPPORTED = 0, 1, 2, 3
 (EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_TANH, EPI_BIAS_RES, EPI_RES_LN, EPI_RELU_LN, EPI_RELU_LN_DOT, EPI_BIAS_LRELU,
  EPI_RES_SUM, EPI_RELU_GRAD) = range(10)
@@ -492,6 +494,67 @@ SIGNATURES_PVOC = {
 }
 
 
+# include/fs2hip_iir.h: cascaded second-order sections, BS.1770 gating, the loudness gain
+SIGNATURES_IIR = {
+    "fs2_iir_blocks": (_i64, [_i64]),
+    "fs2_iir_chunks": (_i64, [_i64]),
+    "fs2_loudness_blocks": (_i64, [_i64, _i64]),
+    "fs2_loudness_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "fs2_sosfilt": (_i, [_p, _i, _i64, _p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "fs2_loudness_gate": (_i, [_p, _p, _i, _i, _i, _d, _d, _p, _p, _p, _i64, _p]),
+    "fs2_gain_int16": (_i, [_p, _i, _i64, _p, _i, _i, _p, _d, _d, _p, _p, _p, _p, _p, _p]),
+}
+
+
+def iir_blocks(n):
+    """iir_blocks of csrc/iir_sizes.h: 0 for n < 1, else ceil(n / 64)."""
+    return 0 if n < 1 else (n - 1) // IIR_BLOCK + 1
+
+
+def iir_chunks(n):
+    """iir_chunks: 0 for n < 1, else ceil(n / 16384)."""
+    return 0 if n < 1 else (n - 1) // IIR_CHUNK + 1
+
+
+def loudness_blocks(n, H):
+    """loud_blocks: the gating blocks of n samples at hop H >= 1, 0 for n < 4 H, else (n - 4 H) // H + 1."""
+    return 0 if n < 1 or n < 4 * H else (n - 4 * H) // H + 1
+
+
+def loudness_workspace_bytes(B, n_max, H):
+    """loud_workspace_bytes: J + 3 sub-block sums and the two tree buffers (J and (J + 1) // 2) per row as
+    f64; 0 for a size below 1 or no block; 2^63 - 1 where it does not fit."""
+    if B < 1 or n_max < 1 or H < 1:
+        return 0
+    J = loudness_blocks(n_max, H)
+    if J < 1:
+        return 0
+    return min(8 * B * ((J + 3) + J + (J + 1) // 2), (1 << 63) - 1)
+
+
+def iir_status(B, n_max, S, row_stride):
+    """iir_check: the status fs2_sosfilt gives these sizes."""
+    if B < 1 or n_max < 1 or S < 1 or row_stride < n_max:
+        return FS2_EINVAL
+    return FS2_EUNSUPPORTED if S > IIR_S_MAX or B > IIR_B_MAX else FS2_OK
+
+
+def loudness_status(B, n_max, H):
+    """loud_check: the status fs2_loudness_gate gives these sizes."""
+    if B < 1 or n_max < 1 or H < 1:
+        return FS2_EINVAL
+    if H > LOUD_H_MAX or B > IIR_B_MAX or loudness_workspace_bytes(B, n_max, H) == (1 << 63) - 1:
+        return FS2_EUNSUPPORTED
+    return FS2_OK
+
+
+def gain_status(B, n_max, row_stride):
+    """gain_check: the status fs2_gain_int16 gives these sizes."""
+    if B < 1 or n_max < 1 or row_stride < n_max:
+        return FS2_EINVAL
+    return FS2_EUNSUPPORTED if B > IIR_B_MAX else FS2_OK
+
+
 def pvoc_frames(T, rate):
     """pvoc_frames of csrc/pvoc_sizes.h: the number of j >= 0 with fl(j * rate) < T, saturated at
     PVOC_J_CAP; 0 for T < 1 and for a rate that is not finite or is <= 0."""
@@ -623,9 +686,10 @@ HEADER_EVAL = os.path.join(os.path.dirname(HEADER), "fs2hip_eval.h")
 HEADER_F0_TRACK = os.path.join(os.path.dirname(HEADER), "fs2hip_f0_track.h")
 HEADER_VAD = os.path.join(os.path.dirname(HEADER), "fs2hip_vad.h")
 HEADER_PVOC = os.path.join(os.path.dirname(HEADER), "fs2hip_pvoc.h")
+HEADER_IIR = os.path.join(os.path.dirname(HEADER), "fs2hip_iir.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
                  "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h",
-                 "fs2hip_pvoc.h")
+                 "fs2hip_pvoc.h", "fs2hip_iir.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -673,7 +737,7 @@ def load():
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
             list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()) + \
-            list(SIGNATURES_PVOC.items()):
+            list(SIGNATURES_PVOC.items()) + list(SIGNATURES_IIR.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -425,3 +425,75 @@ def resample_taps(up, down, beta=5.0):
     c = 1.0 / max(up, down)
     h = c * np.sinc(c * (np.arange(2 * half + 1, dtype=np.float64) - half)) * np.kaiser(2 * half + 1, float(beta))
     return h / h.sum()
+
+
+def k_weighting_sos(sampling_rate):
+    """The K-weighting of ITU-R BS.1770 at ``sampling_rate`` as float64 [2, 6] second-order sections in
+    scipy's layout (b0 b1 b2 1 a1 a2): the high shelf, then the high-pass. The standard tabulates the
+    coefficients at 48 kHz only; this is De Man's bilinear design of the two analogue prototypes, which
+    reproduces that table to all its published digits. With K = tan(pi * f0 / fs) and
+    a0 = 1 + K / Q + K * K, a = [1, 2 * (K * K - 1) / a0, (1 - K / Q + K * K) / a0] for both;
+    the shelf has b = [(Vh + Vb * K / Q + K * K) / a0, 2 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0],
+    the high-pass b = [1, -2, 1]. The bilinear transform warps the shelf as the rate falls: a
+    full-scale 997 Hz sine reads -3.01 LUFS at 48 kHz and about -2.97 at 16 kHz."""
+    import math
+
+    fs = float(sampling_rate)
+    if not fs > 0.0 or not math.isfinite(fs):
+        raise ValueError(f"fs2amd: k_weighting_sos needs a positive sampling rate, got {sampling_rate!r}")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    if not fs > 2.0 * f0:
+        raise ValueError(f"fs2amd: k_weighting_sos needs a sampling rate above {2 * f0:.0f} Hz, got {sampling_rate!r}")
+    K = math.tan(math.pi * f0 / fs)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    high = [1.0, -2.0, 1.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    return np.array([shelf, high], dtype=np.float64)
+
+
+SOS_BLOCK, SOS_TABLE_LEN = 64, 412  # FS2_IIR_BLOCK, FS2_IIR_TABLE_LEN of include/fs2hip_iir.h
+
+
+def sos_tables(sos):
+    """The per-section tables fs2_sosfilt takes (include/fs2hip_iir.h, rule 3), float64 [S, 412], computed
+    in plain Python floats (IEEE double, one rounding per operation, in the header's order): the zero-input
+    responses p and q of the section to the unit states (1, 0) and (0, 1) over one block of 64 samples,
+    the block's state matrix M as P_0, its squarings P_1 .. P_5, and Q_i = M Q_{i-1} for i = 0 .. 64.
+    sos: [S, 6] in scipy's layout with a0 == 1."""
+    sos = np.asarray(sos, dtype=np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6 or sos.shape[0] < 1:
+        raise ValueError("fs2amd: sos must be a float64 [S >= 1, 6] array")
+    if not np.all(sos[:, 3] == 1.0) or not np.all(np.isfinite(sos)):
+        raise ValueError("fs2amd: every section needs a0 == 1 and finite coefficients")
+
+    def mm(A, B):  # row-major 2x2: two products, one add
+        return [A[0] * B[0] + A[1] * B[2], A[0] * B[1] + A[1] * B[3], A[2] * B[0] + A[3] * B[2], A[2] * B[1] + A[3] * B[3]]
+
+    out = np.empty((sos.shape[0], SOS_TABLE_LEN), dtype=np.float64)
+    for s, sec in enumerate(sos.tolist()):
+        a1, a2 = sec[4], sec[5]
+        resp, end = [], []
+        for z1, z2 in ((1.0, 0.0), (0.0, 1.0)):
+            ys = []
+            for _ in range(SOS_BLOCK):
+                y = z1
+                z1 = z2 - a1 * y
+                z2 = -(a2 * y)
+                ys.append(y)
+            resp.append(ys)
+            end.append((z1, z2))
+        M = [end[0][0], end[1][0], end[0][1], end[1][1]]
+        pows = [M]
+        for _ in range(5):
+            pows.append(mm(pows[-1], pows[-1]))
+        Qi = [[1.0, 0.0, 0.0, 1.0]]
+        for _ in range(SOS_BLOCK):
+            Qi.append(mm(M, Qi[-1]))
+        out[s] = np.array(resp[0] + resp[1] + [v for P in pows for v in P] + [v for Q in Qi for v in Q])
+    return out

@@ -2788,3 +2788,142 @@ def phase_vocoder(spec, frames, rates, *, J_max=None, out=None):
     d.frames_out = frames_out.data_ptr() if frames_out is not None else None
     L.check(_lib.fs2_phase_vocoder(ctypes.byref(d), _stream(spec)), "fs2_phase_vocoder")
     return recomb, frames_out
+
+
+SosfiltOut = collections.namedtuple("SosfiltOut", "y y32 zf")
+LoudnessGateOut = collections.namedtuple("LoudnessGateOut", "zbar counts")
+GainOut = collections.namedtuple("GainOut", "q gain clipped unmeasured peak")
+_IIR_DTYPES = {torch.int16: L.FS2_I16, torch.float32: L.FS2_F32, torch.float64: L.FS2_F64}
+
+
+def sos_tables(sos):
+    """The host tables of fs2_sosfilt (include/fs2hip_iir.h, rule 3) for sos [S, 6] (scipy's layout,
+    a0 == 1): a float64 [S, 412] numpy array; ``fs2amd.audio.sos_tables`` computes it."""
+    from .audio import sos_tables as tables
+
+    return tables(sos)
+
+
+def loudness_blocks(n, hop):
+    """fs2_loudness_blocks (include/fs2hip_iir.h): the 400 ms gating blocks of n samples at a hop of
+    ``hop`` samples, 0 for n < 4 * hop, else (n - 4 * hop) // hop + 1."""
+    n, hop = int(n), int(hop)
+    if hop < 1:
+        raise ValueError(f"fs2amd: the gating hop must be at least 1, got {hop}")
+    return L.loudness_blocks(n, hop)
+
+
+def _out_buffers(out, shapes, dev, what):
+    """The buffers of an out= argument checked against (dtype, shape, required) triples, or fresh ones."""
+    if out is None:
+        return tuple(torch.empty(shape, device=dev, dtype=dt) if need else None for dt, shape, need in shapes)
+    if len(out) != len(shapes):
+        raise ValueError(f"fs2amd: {what} takes {len(shapes)} out buffers")
+    for t, (dt, shape, need) in zip(out, shapes):
+        if t is None and not need:
+            continue
+        if t is None or t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"fs2amd: {what} out buffers must be contiguous {dt} {list(shape)} device tensors")
+    return tuple(out)
+
+
+def sosfilt(wav, sos, lens=None, *, zi=None, tables=None, want_y32=False, want_zf=False, out=None):
+    """fs2_sosfilt (include/fs2hip_iir.h): wav int16, float32 or float64 [B, n_max] (unit sample stride,
+    any row stride; ragged through lens [B]) through the cascaded second-order sections sos [S, 6]
+    (scipy's layout, a0 == 1, 1 <= S <= 8; a numpy array or a tensor) -> SosfiltOut(y f64 [B, n_max];
+    y32 f32 [B, n_max] or None; zf f64 [B, S, 2] or None), rows 0 past lens. zi: f64 [B, S, 2] device
+    tensor of starting states (None: zero). tables: the device tensor of ``sos_tables(sos)`` when the
+    caller keeps one (None: computed and uploaded here). It is the recurrence of scipy.signal.sosfilt in
+    this project's blocked float64 order, not scipy's bits. out: (y, y32 or None, zf or None) buffers."""
+    import numpy as np
+
+    _gpu(wav, zi, tables)
+    if wav.dim() != 2 or wav.dtype not in _IIR_DTYPES or wav.shape[1] < 1 or wav.stride(1) != 1:
+        raise ValueError("fs2amd: sosfilt needs an int16, float32 or float64 [B, n_max >= 1] tensor with unit sample stride")
+    B, n_max = wav.shape
+    stride = wav.stride(0) if B > 1 else n_max
+    sos_host = sos.detach().cpu().numpy() if torch.is_tensor(sos) else np.asarray(sos)
+    sos_host = np.ascontiguousarray(sos_host, dtype=np.float64)
+    if sos_host.ndim != 2 or sos_host.shape[1] != 6:
+        raise ValueError("fs2amd: sos must be [S, 6]")
+    S = sos_host.shape[0]
+    rc = L.iir_status(B, n_max, S, stride)
+    if rc == L.FS2_EINVAL:
+        raise ValueError(f"fs2amd: sosfilt needs B, n_max, S >= 1 and rows that do not overlap (row stride {stride})")
+    if rc != L.FS2_OK:
+        raise ValueError(f"fs2amd: sosfilt takes at most {L.IIR_S_MAX} sections and {L.IIR_B_MAX} rows, got {S}, {B}")
+    dev = wav.device
+    if tables is None:
+        tables = torch.from_numpy(sos_tables(sos_host)).to(dev)
+    elif tables.dtype != torch.float64 or tuple(tables.shape) != (S, L.IIR_TABLE_LEN) or not tables.is_contiguous():
+        raise ValueError(f"fs2amd: tables must be a contiguous float64 [{S}, {L.IIR_TABLE_LEN}] tensor")
+    elif not np.all(sos_host[:, 3] == 1.0):
+        raise ValueError("fs2amd: every section needs a0 == 1")
+    sos_dev = torch.from_numpy(sos_host).to(dev)
+    if zi is not None and (zi.dtype != torch.float64 or tuple(zi.shape) != (B, S, 2) or not zi.is_contiguous()):
+        raise ValueError(f"fs2amd: zi must be a contiguous float64 [{B}, {S}, 2] tensor")
+    lens_dev, _ = _lengths_arg(lens, B, dev, "lens")
+    _gpu(lens_dev)
+    y, y32, zf = _out_buffers(out, ((torch.float64, (B, n_max), True), (torch.float32, (B, n_max), want_y32),
+                                    (torch.float64, (B, S, 2), want_zf)), dev, "sosfilt")
+    L.check(_lib.fs2_sosfilt(_ptr(wav), _IIR_DTYPES[wav.dtype], stride, _ptr(lens_dev), B, n_max, _ptr(sos_dev),
+                             _ptr(tables), S, _ptr(zi), _ptr(y), _ptr(y32), _ptr(zf), _stream(wav)), "fs2_sosfilt")
+    return SosfiltOut(y, y32, zf)
+
+
+def loudness_gate(y, lens=None, *, hop, abs_gate, rel_factor=0.1, out=None):
+    """fs2_loudness_gate (include/fs2hip_iir.h): the BS.1770-4 gating of K-weighted rows y f64 [B, n_max]
+    (contiguous; ragged through lens [B]) with blocks of 4 * hop samples every hop ->
+    LoudnessGateOut(zbar f64 [B], the mean square over the blocks that pass both gates, +0.0 where none
+    does; counts int32 [B, 3] = (blocks, above the absolute gate, above both)). abs_gate is in the units
+    of y squared. out: (zbar, counts) buffers to write into."""
+    _gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float64 or y.shape[1] < 1 or not y.is_contiguous():
+        raise ValueError("fs2amd: loudness_gate needs a contiguous float64 [B, n_max >= 1] tensor")
+    B, n_max = y.shape
+    H = int(hop)
+    rc = L.loudness_status(B, n_max, H)
+    if rc == L.FS2_EINVAL:
+        raise ValueError(f"fs2amd: loudness_gate needs B, n_max and hop >= 1, got {B}, {n_max}, {H}")
+    if rc != L.FS2_OK:
+        raise ValueError(f"fs2amd: loudness_gate takes a hop of at most {L.LOUD_H_MAX} and {L.IIR_B_MAX} rows, got {H}, {B}")
+    if not (float(abs_gate) >= 0.0 and float(rel_factor) >= 0.0):
+        raise ValueError("fs2amd: abs_gate and rel_factor are non-negative numbers")
+    lens_dev, _ = _lengths_arg(lens, B, y.device, "lens")
+    _gpu(lens_dev)
+    zbar, counts = _out_buffers(out, ((torch.float64, (B,), True), (torch.int32, (B, 3), True)), y.device, "loudness_gate")
+    ws_bytes = int(_lib.fs2_loudness_workspace_bytes(B, n_max, H))
+    ws = torch.empty(ws_bytes // 8, device=y.device, dtype=torch.float64) if ws_bytes > 0 else None
+    L.check(_lib.fs2_loudness_gate(_ptr(y), _ptr(lens_dev), B, n_max, H, float(abs_gate), float(rel_factor), _ptr(zbar),
+                                   _ptr(counts), _ptr(ws), ws_bytes, _stream(y)), "fs2_loudness_gate")
+    return LoudnessGateOut(zbar, counts)
+
+
+def gain_int16(wav, zbar, lens=None, *, target_z, peak_ceiling=None, out=None):
+    """fs2_gain_int16 (include/fs2hip_iir.h): wav int16 or float32 [B, n_max] times the row gain
+    sqrt(target_z / zbar[b]) (1.0, and unmeasured, where zbar[b] is 0), lowered to peak_ceiling / max |wav|
+    where it exceeds that (peak_ceiling None: no ceiling) -> GainOut(q of wav's dtype [B, n_max]: int16
+    rounded to nearest even and saturated, float32 not saturated; gain f64 [B]; clipped int32 [B], the
+    saturated samples; unmeasured int32 [B]; peak f64 [B], or None without a ceiling). out: (q, gain,
+    clipped, unmeasured, peak or None) buffers to write into."""
+    _gpu(wav, zbar)
+    B, n_max, stride, dtype = _wav_rows(wav, "gain_int16")
+    rc = L.gain_status(B, n_max, stride)
+    if rc != L.FS2_OK:
+        raise ValueError(f"fs2amd: gain_int16 takes at most {L.IIR_B_MAX} rows, got {B}")
+    if zbar.dtype != torch.float64 or tuple(zbar.shape) != (B,) or not zbar.is_contiguous():
+        raise ValueError(f"fs2amd: zbar must be a contiguous float64 [{B}] tensor")
+    import math
+
+    ceiling = 0.0 if peak_ceiling is None else float(peak_ceiling)
+    if not (float(target_z) > 0.0 and math.isfinite(float(target_z))) or not ceiling >= 0.0:
+        raise ValueError("fs2amd: target_z is a positive number and peak_ceiling a non-negative one")
+    lens_dev, _ = _lengths_arg(lens, B, wav.device, "lens")
+    _gpu(lens_dev)
+    q, gain, clipped, unmeasured, peak = _out_buffers(
+        out, ((wav.dtype, (B, n_max), True), (torch.float64, (B,), True), (torch.int32, (B,), True),
+              (torch.int32, (B,), True), (torch.float64, (B,), ceiling > 0.0)), wav.device, "gain_int16")
+    L.check(_lib.fs2_gain_int16(_ptr(wav), dtype, stride, _ptr(lens_dev), B, n_max, _ptr(zbar), float(target_z), ceiling,
+                                _ptr(q), _ptr(gain), _ptr(clipped), _ptr(unmeasured), _ptr(peak), _stream(wav)),
+            "fs2_gain_int16")
+    return GainOut(q, gain, clipped, unmeasured, peak)

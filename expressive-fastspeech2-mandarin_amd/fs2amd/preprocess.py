@@ -225,7 +225,7 @@ def split_silence(wavs, *, top_db=60.0, frame_length=2048, hop_length=512, min_s
 
 
 def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=None, trim_db=None,
-                 trim_frame_length=2048, trim_hop_length=512, trim_margin=0):
+                 trim_frame_length=2048, trim_hop_length=512, trim_margin=0, lufs=None, lufs_peak_ceiling=None):
     """The reference's prepare_align arithmetic (preprocessor/esd_chinese.py:145-147) for a list of
     1-D int16 / float32 waveforms at the source rates ``rates`` (one per waveform, or one number for
     all): resampled to ``sampling_rate``, divided by the peak, scaled by max_wav_value and cut to
@@ -236,11 +236,22 @@ def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=No
     comes out as 32767 where the reference's cast wraps. An all-zero waveform stays zero.
     trim_db: None, or the top_db of ``trim_silence``: every group is then trimmed on the device after
     the int16 pass and before the copy back (frames of trim_frame_length every trim_hop_length,
-    trim_margin samples kept on either side); on int16 rows every sum of the frame power is exact."""
+    trim_margin samples kept on either side); on int16 rows every sum of the frame power is exact.
+    lufs: None, or a target in LUFS: every group is then brought to that integrated loudness on the
+    device (``fs2amd.loudness``: BS.1770 K-weighting and gating at ``sampling_rate``, one gain per
+    waveform, int16 rounded to nearest and saturated) after the int16 pass and after the trim, before
+    the copy back. lufs_peak_ceiling: None, or the largest |sample| allowed as a fraction of full
+    scale; the gain is lowered where it would exceed that. A waveform with no block above the gates
+    (shorter than 400 ms, or silent) keeps its peak-normalised samples. None runs nothing more."""
     from . import ops
     from .audio import resample_ratio, resample_taps
 
     dev = _device(device)
+    kw = None
+    if lufs is not None:
+        from . import loudness
+
+        kw = loudness.KWeighting(sampling_rate, dev)
     wavs = [np.asarray(w) for w in wavs]
     if any(w.ndim != 1 or w.dtype not in (np.int16, np.float32) for w in wavs):
         raise ValueError("fs2amd: waveforms are 1-D int16 or float32 arrays")
@@ -266,6 +277,11 @@ def prepare_wavs(wavs, rates, *, sampling_rate, max_wav_value=32768.0, device=No
                                     hop_length=trim_hop_length, min_silence=1, margin=trim_margin)
             q, cut_lens = ops.cut_rows(q, trim[:, 0].contiguous(), trim[:, 1].contiguous())
             out_lens = cut_lens.cpu().tolist()
+        if kw is not None:
+            ceiling = None if lufs_peak_ceiling is None else float(lufs_peak_ceiling) * 32768.0
+            _, r = loudness.normalize_batch(q, torch.as_tensor(out_lens, dtype=torch.int64).to(dev), kw,
+                                            target_lufs=lufs, peak_ceiling=ceiling)
+            q = r.q
         q = q.cpu().numpy()
         for j, b in enumerate(idx):
             res[b] = q[j, :out_lens[j]].copy()
@@ -370,7 +386,7 @@ def _aligned_durations(batch, wav_dev, lens, stft, aligner):
 
 
 def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None, seed=1234, batch_size=16,
-                 emotions=None, aligner=None, f0_method="yin", trim_db=None, trim_margin=0):
+                 emotions=None, aligner=None, f0_method="yin", trim_db=None, trim_margin=0, lufs=None):
     """Write a preprocessed corpus directory (preprocessor.py:116-224, :304-325) from utterances, an
     iterable of dicts with ``basename``, ``speaker``, ``phones`` (list of labels), ``raw_text``,
     ``aux`` (the metadata tail, e.g. "emotion|arousal|valence"), ``wav`` (1-D float32 in [-1, 1] or
@@ -398,6 +414,10 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
     refer to the trimmed waveform: durations that sum to more frames than its mel has raise a ValueError
     (everywhere else durations are expected to fit, as ``extract_features`` says). An utterance that
     trims to nothing is dropped, as an all-silence TextGrid is.
+    lufs: None, or a target in LUFS handed to ``prepare_wavs`` for the utterances that go through it
+    (the ones that name their ``sampling_rate``): they are loudness-normalised after the peak
+    normalisation, before the ``start`` / ``end`` cut and the trim; the gating makes the measurement
+    indifferent to the silence those remove. None changes nothing.
 
     Utterances go through extract_features, pitch_targets and two CorpusStats in batches of
     batch_size; the ones the reference drops (at most one voiced frame) are left out. Pitch and
@@ -433,7 +453,8 @@ def build_corpus(out_dir, utterances, preprocess_config, *, stft, val_size=None,
         own = [b for b, u in enumerate(batch) if u.get("sampling_rate") is not None]
         if own:
             ready = prepare_wavs([wavs[b] for b in own], [batch[b]["sampling_rate"] for b in own], sampling_rate=sr,
-                                 max_wav_value=pp["audio"].get("max_wav_value", 32768.0), device=dev)
+                                 max_wav_value=pp["audio"].get("max_wav_value", 32768.0), device=dev,
+                                 **({} if lufs is None else {"lufs": lufs}))
             for b, w in zip(own, ready):
                 wavs[b] = w
         for b, u in enumerate(batch):
