@@ -22,6 +22,7 @@
 
 #include "conv_common.h"
 #include "fs2_common.h"
+#include "fs2hip_postnet.h"
 
 namespace {
 
@@ -486,10 +487,34 @@ struct PnHeadArgs {
   const int2 *row_pos;
   const int32_t *rows_dev;
   int out_sc1;
+  // H3 (fs2_pn_head3): mel_linear in the prologue, the third conv on the y2 tile
+  const bf16 *dx;         // decoder rows [*, >= 256] (packed through rowmap, or the padded rows)
+  int64_t dxs;
+  uint32_t dx_bytes;
+  const int32_t *rowmap;  // decoder row of padded row m (-1: a padded frame), or NULL
+  const bf16 *wm;         // mel_linear weights [80][256]
+  const float *bm;
+  float *mel;             // f32 [M, >= 80]
+  int64_t mels;
+  bf16 *mel_bf;           // optional bf16 copy [M, 80] (NULL: the bf16 mel stays on chip)
+  const bf16 *w3;
+  const float *b3;
 };
 
+// H3: the PostNet's first THREE convolutions and mel_linear before them in one launch. A workgroup
+// owns TB = 108 rows of y3 and starts 2 rows early, as the fused tail does (m0 = 108 i - 2): the
+// decoder rows of its 120 mel rows are DMA'd (through the row map; a padded frame reads zeros) into
+// the y1 region beside mel_linear's 80 x 256 weights, mel = x W^T + b runs on the MFMA fs2_conv1d
+// uses for this shape (x rows on the A side, ascending k: the same bits), bf16(mel) becomes the
+// mel tile and the f32 rows the workgroup owns go to [M, 80]. After conv2, y2 = bf16(tanh(acc +
+// b2)) is written over y1 at the same pitch and wconv's main loop runs once more with the third
+// conv's weights (rows 108..111 of that pass and taps that leave a sequence read the zero region).
+// Gone: two launches, the bf16 mel and the y2 round trips (4.4 + 56 MB), one x-tile prologue.
+template <bool H3>
 __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
   constexpr int KS = 5, CIN1 = 80, NCOL = 512, MB = 7, BM = 112, NWV = 8, NT = 512, JB = 4, DEPTH = 4;
+  constexpr int TB = H3 ? BM - (KS - 1) : BM;  // rows of the last conv's output a workgroup stores
+  constexpr int RO = H3 ? (KS - 1) / 2 : 0;    // ... from tile row RO on
   constexpr int YR = BM + KS - 1;            // y1 rows: m0 - 2 .. m0 + 113
   constexpr int XR = BM + 2 * (KS - 1);      // mel rows: m0 - 4 .. m0 + 115
   constexpr int YPITCH = NCOL * 2 + 32;      // 1056: conflict-free fragment reads for any tap
@@ -506,36 +531,83 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
   constexpr int X_OFF = Y_OFF + YREG;
   constexpr int B1_OFF = X_OFF + NWV * XPW * 1024;
   constexpr int B2_OFF = B1_OFF + NCOL * 4;
-  constexpr int SMEM = B2_OFF + NCOL * 4;
+  constexpr int B3_OFF = B2_OFF + NCOL * 4;
+  // H3 prologue, inside the y1 region: the decoder rows (256 channels at a 528-byte pitch: a
+  // fragment's 16 rows in 16 distinct bank groups; 8 pieces per wave cover the 120 rows) and
+  // mel_linear's weights at the same pitch (6 pieces per wave cover the 80 rows)
+  constexpr int DK = 256, NM = 80, DPITCH = DK * 2 + 16, DPW = 8, WMPW = 6;
+  constexpr int WM_OFF = Y_OFF + NWV * DPW * 1024;
+  constexpr int BM_OFF = B3_OFF + NCOL * 4;
+  static_assert(XR * DPITCH <= NWV * DPW * 1024 && NM * DPITCH <= NWV * WMPW * 1024, "prologue pieces");
+  static_assert(WM_OFF + NWV * WMPW * 1024 <= Y_OFF + YREG && 128 * DPITCH <= YREG, "prologue fits the y1 region");
+  constexpr int SMEM = H3 ? BM_OFF + NM * 4 : B2_OFF + NCOL * 4;
   static_assert(SMEM <= 163840, "LDS");
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int M = p.rows_dev != nullptr ? min(*p.rows_dev, p.M) : p.M, T = p.T, pad = p.pad;
-  const int m0 = blockIdx.x * BM;
-  if (m0 >= M) return;
+  const int M = !H3 && p.rows_dev != nullptr ? min(*p.rows_dev, p.M) : p.M, T = p.T, pad = p.pad;
+  if ((int)blockIdx.x * TB >= M) return;
+  const int m0 = (int)blockIdx.x * TB - RO;
   const int hrow0 = lane & 15, hi = lane >> 4;
   auto taps = [&](int gm) {  // bit tap: row gm's tap stays inside its sequence
     int v = 0;
     if (gm >= 0 && gm < M) {
       int tpos, tlen;
-      seq_pos(p.row_pos, gm, T, tpos, tlen);
+      seq_pos(H3 ? nullptr : p.row_pos, gm, T, tpos, tlen);  // H3: padded rows only
 #pragma unroll
       for (int tap = 0; tap < KS; ++tap) v |= ((unsigned)(tpos + tap - pad) < (unsigned)tlen ? 1 : 0) << tap;
     }
     return v;
   };
   for (int i = tid; i < ZBYTES / 16; i += NT) *reinterpret_cast<float4 *>(smem + 16 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  // b1 | b2 -> LDS by LDS-DMA (waves 0..3, one 1 KiB piece each; B2_OFF = B1_OFF + 2 KiB)
-  if (w < 4)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(w < 2 ? p.b1 : p.b2, NCOL * 4),
+  // b1 | b2 (| b3) -> LDS by LDS-DMA (waves 0..3 (..5), one 1 KiB piece each; 2 KiB per bias)
+  if (w < (H3 ? 6 : 4))
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(w < 2 ? p.b1 : (w < 4 ? p.b2 : p.b3), NCOL * 4),
                                              (__attribute__((address_space(3))) void *)(smem + B1_OFF + w * 1024), 16,
                                              (uint32_t)((w & 1) * 1024 + lane * 16), 0, 0, 0);
 
+  const rsrc_t w1r = make_rsrc(p.w1, p.w1_bytes), w2r = make_rsrc(p.w2, p.w2_bytes);
+  const rsrc_t w3r = make_rsrc(H3 ? p.w3 : p.w2, p.w2_bytes);
+  if constexpr (H3) {
+    // the decoder rows of mel rows m0 - 4 .. m0 + 115 and mel_linear's weights -> the y1 region
+    // (lane-linear 1 KiB pieces at the padded pitch; a padded frame or a row outside [0, M): zeros)
+    if (w == 7 && lane < NM / 4)
+      *reinterpret_cast<float4 *>(smem + BM_OFF + 16 * lane) = reinterpret_cast<const float4 *>(p.bm)[lane];
+    // mel tile rows past XR: conv1's dropped row blocks read them
+    for (int i = tid; i < (NWV * XPW * 1024 - XR * XPITCH) / 16; i += NT)
+      *reinterpret_cast<float4 *>(smem + X_OFF + XR * XPITCH + 16 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    int src[DPW];
+#pragma unroll
+    for (int i = 0; i < DPW; ++i) {
+      const int r = ((w + NWV * i) * 1024 + lane * 16) / DPITCH;
+      const int gm = m0 - 2 * pad + r;
+      src[i] = -1;
+      if (r < XR && gm >= 0 && gm < M) src[i] = p.rowmap != nullptr ? p.rowmap[gm] : gm;
+    }
+    const rsrc_t wmr = make_rsrc(p.wm, NM * DK * 2), dr = make_rsrc(p.dx, p.dx_bytes);
+#pragma unroll
+    for (int i = 0; i < WMPW; ++i) {
+      const int pc = w + NWV * i;
+      const int o = pc * 1024 + lane * 16;
+      const int r = o / DPITCH, within = o - r * DPITCH;
+      const bool ok = r < NM && within < DK * 2;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wmr, (__attribute__((address_space(3))) void *)(smem + WM_OFF + pc * 1024),
+                                               16, ok ? (uint32_t)(r * DK * 2 + within) : kOOB, 0, 0, 0);
+    }
+    const uint32_t drow = (uint32_t)p.dxs * 2u;
+#pragma unroll
+    for (int i = 0; i < DPW; ++i) {
+      const int pc = w + NWV * i;
+      const int o = pc * 1024 + lane * 16;
+      const int within = o - (o / DPITCH) * DPITCH;
+      const bool ok = src[i] >= 0 && within < DK * 2;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(dr, (__attribute__((address_space(3))) void *)(smem + Y_OFF + pc * 1024),
+                                               16, ok ? (uint32_t)src[i] * drow + (uint32_t)within : kOOB, 0, 0, 0);
+    }
+  } else {
   // mel tile -> LDS (lane-linear 1 KiB pieces at the padded pitch)
   const rsrc_t xr = make_rsrc(p.x, p.x_bytes);
-  const rsrc_t w1r = make_rsrc(p.w1, p.w1_bytes), w2r = make_rsrc(p.w2, p.w2_bytes);
   const uint32_t xrow = (uint32_t)p.xs * 2u;
 #pragma unroll
   for (int i = 0; i < XPW; ++i) {
@@ -547,27 +619,71 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (__attribute__((address_space(3))) void *)(smem + X_OFF + pc * 1024),
                                              16, ok ? (uint32_t)gm * xrow + (uint32_t)within : kOOB, 0, 0, 0);
   }
+  }
 
   // one weight stream per wave: units 0..12 of conv1 twice (two row passes), then conv2's 80
+  // (H3: then conv3's 80)
   const uint32_t lane_off = (uint32_t)lane * 16u;
   const uint32_t wb1 = (uint32_t)(w * NU1) * (uint32_t)kUnitB, wb2 = (uint32_t)(w * NU2) * (uint32_t)kUnitB;
   bf16x8 pa[DEPTH][JB];
   auto load_at = [&](auto S, int u) {  // u: position in the stream (past the end: a harmless reload)
     constexpr int s = decltype(S)::value;
-    const bool c1 = u < 2 * NU1;
-    const int uu = c1 ? (u < NU1 ? u : u - NU1) : (u - 2 * NU1 < NU2 ? u - 2 * NU1 : 0);
-    const rsrc_t r = c1 ? w1r : w2r;
+    const bool c1 = u < 2 * NU1, c2 = !H3 || u < 2 * NU1 + NU2;
+    const int u2 = c2 ? u - 2 * NU1 : u - 2 * NU1 - NU2;
+    const int uu = c1 ? (u < NU1 ? u : u - NU1) : (u2 < NU2 ? u2 : 0);
+    const rsrc_t r = c1 ? w1r : (c2 ? w2r : w3r);
     const uint32_t so = (c1 ? wb1 : wb2) + (uint32_t)uu * (uint32_t)kUnitB;
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb)
-      pa[s][jb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, lane_off + jb * 1024, so, 0));
+      if constexpr (H3)  // the block offset on the scalar side: one lane-offset register, not four
+        pa[s][jb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, lane_off, so + jb * 1024, 0));
+      else
+        pa[s][jb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, lane_off + jb * 1024, so, 0));
     __builtin_amdgcn_sched_barrier(0);
   };
   static_for<DEPTH>([&](auto S) { load_at(S, decltype(S)::value); });
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * DEPTH) : "memory");
   __builtin_amdgcn_s_waitcnt(kLgkm0);
   __syncthreads();
+
+  if constexpr (H3) {
+    // ---- mel_linear: wave w owns mel rows 16w .. 16w+15 (x rows on the A side) x the 5 column
+    // blocks; k ascending in 32-wide slices, as conv_gemm's 64-wide k-steps of two slices run
+    f32x4 am[NM / 16];
+#pragma unroll
+    for (int nb = 0; nb < NM / 16; ++nb) am[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const char *ab = smem + Y_OFF + (16 * w + hrow0) * DPITCH + hi * 16;
+    const char *bb = smem + WM_OFF + hrow0 * DPITCH + hi * 16;
+#pragma unroll
+    for (int s = 0; s < DK / 32; ++s) {
+      const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(ab + s * 64);
+#pragma unroll
+      for (int nb = 0; nb < NM / 16; ++nb)
+        am[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            fa, *reinterpret_cast<const bf16x8 *>(bb + nb * 16 * DPITCH + s * 64), am[nb], 0, 0, 0);
+    }
+    // + bias: bf16 -> the mel tile (rows outside [0, M): zeros, as the tile DMA gives), f32 -> the
+    // rows this workgroup owns (mel tile rows 6 .. 113); lane: column 16 nb + hrow0, rows 4 hi + v
+#pragma unroll
+    for (int nb = 0; nb < NM / 16; ++nb) {
+      const int n = nb * 16 + hrow0;
+      const float bn = *reinterpret_cast<const float *>(smem + BM_OFF + 4 * n);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int r = 16 * w + 4 * hi + v, gm = m0 - 2 * pad + r;
+        const bool in = gm >= 0 && gm < M;
+        const float y = am[nb][v] + bn;
+        if (r < XR) *reinterpret_cast<bf16 *>(smem + X_OFF + r * XPITCH + n * 2) = in ? (bf16)y : (bf16)0.0f;
+        if (in && r >= 2 * pad + RO && r < 2 * pad + RO + TB) {
+          p.mel[(size_t)gm * p.mels + n] = y;
+          if (p.mel_bf != nullptr) p.mel_bf[(size_t)gm * NM + n] = (bf16)y;
+        }
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(kLgkm0);
+    __syncthreads();  // mel tile visible; the decoder rows and weights are dead (y1 overwrites them)
+  }
 
   // ---- conv1 in two passes of 4 row blocks (y1 rows 0..63, 64..127; rows >= 116 are dropped)
   static_for<2>([&](auto PASS) {
@@ -631,12 +747,13 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
   __builtin_amdgcn_s_waitcnt(kLgkm0);
   __syncthreads();  // y1 visible
 
-  // ---- conv2 on the y1 tile (wconv's main loop)
+  // ---- conv2 on the y1 tile (wconv's main loop); H3: once more on the y2 tile
   int vm2[MB];  // (computed here: kept live through conv1 they cost a spill)
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) vm2[mb] = taps(m0 + mb * 16 + hrow0);
+  int lbase = Y_OFF + hrow0 * YPITCH + hi * 16;  // this lane's fragment address in tile row 0
   auto bases_x = [&](int tap, int (&ad)[MB]) {
-    const int base = Y_OFF + (hrow0 + tap) * YPITCH + hi * 16;
+    const int base = lbase + tap * YPITCH;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) ad[mb] = (base + mb * 16 * YPITCH) & __builtin_amdgcn_sbfe(vm2[mb], tap, 1);
   };
@@ -647,10 +764,6 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
     for (int mb = 0; mb < MB; ++mb) f[mb] = *reinterpret_cast<const bf16x8 *>(smem + ad[mb] + off);
   };
   f32x4 acc[JB][MB];
-#pragma unroll
-  for (int i = 0; i < JB; ++i)
-#pragma unroll
-    for (int j = 0; j < MB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto mma = [&](const bf16x8 (&fa)[JB], const bf16x8 (&fb)[MB]) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
@@ -658,13 +771,20 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
       for (int jb = 0; jb < JB; ++jb)
         acc[jb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[jb], fb[mb], acc[jb][mb], 0, 0, 0);
   };
-  constexpr int S0 = 2 * NU1;  // stream position of conv2's unit 0
+  auto conv512 = [&](auto S0C) {  // S0C: stream position of the conv's unit 0
+  constexpr int S0 = decltype(S0C)::value;
+#pragma unroll
+  for (int i = 0; i < JB; ++i)
+#pragma unroll
+    for (int j = 0; j < MB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   int bxc[MB], bxn[MB];
   bases_x(0, bxc);
   issue_x(bxc, std::integral_constant<int, 0>{}, f0);
 #pragma nounroll
   for (int tap = 0; tap < KS; ++tap) {
-    bases_x(tap + 1, bxn);  // tap KS: every row masked (zero region), a harmless read
+    // tap KS: every row masked (zero region), a harmless read. H3 derives the next tap's bases
+    // where the current ones die (7 registers fewer through the loop: no spill inside it)
+    if constexpr (!H3) bases_x(tap + 1, bxn);
     static_for<NKS>([&](auto KSI) {
       constexpr int ks = decltype(KSI)::value, sl = (S0 + ks) % DEPTH;
       if constexpr (ks + 1 < NKS) {
@@ -673,6 +793,7 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
         else
           issue_x(bxc, std::integral_constant<int, ks + 1>{}, f1);
       } else {
+        if constexpr (H3) bases_x(tap + 1, bxn);
         issue_x(bxn, std::integral_constant<int, 0>{}, f0);
       }
       if constexpr (ks & 1)
@@ -684,15 +805,51 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) bxc[mb] = bxn[mb];
   }
+  };
+  conv512(std::integral_constant<int, 2 * NU1>{});
+  int tE = tid;  // the epilogues' thread index
+  if constexpr (H3) {
+    // y2 = bf16(tanh(acc + b2)) over y1 at the x pitch (tile row r: row m0 + r), then conv3: its
+    // output row r is row m0 + 2 + r and reads tile rows r .. r + 4; rows >= TB are not stored
+    __builtin_amdgcn_s_waitcnt(kLgkm0);
+    __syncthreads();  // every wave's reads of y1 are done
+    // (opaque after each conv: what the epilogues and conv3's masks derive from the lane is
+    // computed where it is used, not hoisted above a main loop and kept live or spilled through it)
+    asm volatile("" : "+v"(tE));
+    const int hrow0 = tE & 15, hi = (tE & 63) >> 4;
+#pragma unroll
+    for (int nb = 0; nb < JB; ++nb) {
+      const int n = w * 64 + nb * 16 + 4 * hi;
+      const float4 bb = *reinterpret_cast<const float4 *>(smem + B2_OFF + 4 * n);
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        const f32x4 v = acc[nb][mb];
+        bf16x4 o;
+        o[0] = (bf16)tanh_fast(v[0] + bb.x);
+        o[1] = (bf16)tanh_fast(v[1] + bb.y);
+        o[2] = (bf16)tanh_fast(v[2] + bb.z);
+        o[3] = (bf16)tanh_fast(v[3] + bb.w);
+        *reinterpret_cast<bf16x4 *>(smem + Y_OFF + (hrow0 + mb * 16) * YPITCH + n * 2) = o;
+      }
+    }
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) vm2[mb] = mb * 16 + hrow0 < TB ? taps(m0 + RO + mb * 16 + hrow0) : 0;
+    lbase = Y_OFF + hrow0 * YPITCH + hi * 16;
+    __builtin_amdgcn_s_waitcnt(kLgkm0);
+    __syncthreads();  // y2 visible
+    conv512(std::integral_constant<int, 2 * NU1 + NU2>{});
+    asm volatile("" : "+v"(tE));
+  }
 
-  // epilogue: + b2, tanh, bf16 -> LDS staging (the y1 region) -> whole-row stores
+  // epilogue: + b2 (H3: b3), tanh, bf16 -> LDS staging (the y1 region) -> whole-row stores
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_waitcnt(kLgkm0);
   __syncthreads();
+  const int hrE = tE & 15, hiE = (tE & 63) >> 4;
 #pragma unroll
   for (int nb = 0; nb < JB; ++nb) {
-    const int n = w * 64 + nb * 16 + 4 * hi;
-    const float4 bb = *reinterpret_cast<const float4 *>(smem + B2_OFF + 4 * n);
+    const int n = w * 64 + nb * 16 + 4 * hiE;
+    const float4 bb = *reinterpret_cast<const float4 *>(smem + (H3 ? B3_OFF : B2_OFF) + 4 * n);
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
       const f32x4 v = acc[nb][mb];
@@ -701,7 +858,7 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
       o[1] = (bf16)tanh_fast(v[1] + bb.y);
       o[2] = (bf16)tanh_fast(v[2] + bb.z);
       o[3] = (bf16)tanh_fast(v[3] + bb.w);
-      *reinterpret_cast<bf16x4 *>(smem + Y_OFF + (hrow0 + mb * 16) * OPITCH + n * 2) = o;
+      *reinterpret_cast<bf16x4 *>(smem + Y_OFF + (hrE + mb * 16) * OPITCH + n * 2) = o;
     }
   }
   __syncthreads();
@@ -709,10 +866,10 @@ __global__ __launch_bounds__(512, 1) void pn_head_kernel(PnHeadArgs p) {
   char *ob = reinterpret_cast<char *>(p.out);
   const uint32_t orow = (uint32_t)p.os * 2u;
 #pragma unroll 2
-  for (int i = tid; i < BM * CPR; i += NT) {
+  for (int i = tE; i < BM * CPR; i += NT) {
     const int m = i / CPR, ch = i - m * CPR;
-    if (m0 + m < M)
-      store16_out(ob, (uint32_t)(m0 + m) * orow + (uint32_t)ch * 16u,
+    if (m < TB && m0 + RO + m < M)
+      store16_out(ob, (uint32_t)(m0 + RO + m) * orow + (uint32_t)ch * 16u,
                   *reinterpret_cast<const uint4 *>(smem + Y_OFF + m * OPITCH + ch * 16), p.out_sc1);
   }
 }
@@ -997,11 +1154,59 @@ extern "C" int fs2_wconv(const fs2_wconv_desc *d, fs2_stream_t stream) {
     q.row_pos = row_pos;
     q.rows_dev = d->rows_dev;
     q.out_sc1 = env_out_sc1();
-    hipLaunchKernelGGL(pn_head_kernel, dim3(nwg), dim3(512), 0, as_stream(stream), q);
+    hipLaunchKernelGGL(pn_head_kernel<false>, dim3(nwg), dim3(512), 0, as_stream(stream), q);
   } else if (d->Cin == 80)
     hipLaunchKernelGGL((wconv_kernel<5, 80, 1>), dim3(nwg), dim3(512), 0, as_stream(stream), p);
   else
     hipLaunchKernelGGL((wconv_kernel<5, 512, WCONV_WQ>), dim3(nwg), dim3(512 / WCONV_WQ), 0, as_stream(stream), p);
+  FS2_CHECK_LAUNCH();
+  return FS2_OK;
+}
+
+extern "C" int fs2_pn_head3(const fs2_pn_head3_desc *d, fs2_stream_t stream) {
+  if (d == nullptr || d->x == nullptr || d->mel_w == nullptr || d->mel_b == nullptr || d->mel == nullptr ||
+      d->out == nullptr)
+    return FS2_EINVAL;
+  for (int i = 0; i < 3; ++i)
+    if (d->w[i] == nullptr || d->bias[i] == nullptr) return FS2_EINVAL;
+  if (d->B < 0 || d->T < 0 || d->x_rows < 0 || d->x_row_stride < 256 || (d->x_row_stride & 7) ||
+      d->mel_row_stride < 80 || d->out_row_stride < 512 || (d->out_row_stride & 7))
+    return FS2_EINVAL;
+  const int64_t M64 = (int64_t)d->B * d->T;
+  if (M64 == 0) return FS2_OK;
+  if (d->rowmap == nullptr && d->x_rows < M64) return FS2_EINVAL;
+  const int64_t xb = d->x_rows * d->x_row_stride * 2, ob = M64 * d->out_row_stride * 2;
+  if (xb >= (1LL << 31) || ob >= (1LL << 32) || M64 > 0x7fffff00LL) return FS2_EUNSUPPORTED;
+  PnHeadArgs q;
+  q.x = nullptr;
+  q.xs = 0;
+  q.x_bytes = 0;
+  q.w1 = reinterpret_cast<const bf16 *>(d->w[0]);
+  q.w2 = reinterpret_cast<const bf16 *>(d->w[1]);
+  q.w3 = reinterpret_cast<const bf16 *>(d->w[2]);
+  q.b1 = d->bias[0];
+  q.b2 = d->bias[1];
+  q.b3 = d->bias[2];
+  q.out = reinterpret_cast<bf16 *>(d->out);
+  q.os = d->out_row_stride;
+  q.T = d->T;
+  q.M = (int)M64;
+  q.pad = 2;
+  q.w1_bytes = (uint32_t)(fs2_wconv_weight_elems(5, 80, 512) * 2);
+  q.w2_bytes = (uint32_t)(fs2_wconv_weight_elems(5, 512, 512) * 2);
+  q.row_pos = nullptr;
+  q.rows_dev = nullptr;
+  q.out_sc1 = env_out_sc1();
+  q.dx = reinterpret_cast<const bf16 *>(d->x);
+  q.dxs = d->x_row_stride;
+  q.dx_bytes = (uint32_t)xb;
+  q.rowmap = d->rowmap;
+  q.wm = reinterpret_cast<const bf16 *>(d->mel_w);
+  q.bm = d->mel_b;
+  q.mel = d->mel;
+  q.mels = d->mel_row_stride;
+  q.mel_bf = reinterpret_cast<bf16 *>(d->mel_bf16);
+  hipLaunchKernelGGL(pn_head_kernel<true>, dim3((unsigned)((M64 + 107) / 108)), dim3(512), 0, as_stream(stream), q);
   FS2_CHECK_LAUNCH();
   return FS2_OK;
 }

@@ -135,6 +135,16 @@ class WconvDesc(ctypes.Structure):
     ]
 
 
+class PnHead3Desc(ctypes.Structure):
+    """Mirror of ``fs2_pn_head3_desc`` (include/fs2hip_postnet.h)."""
+
+    _fields_ = [
+        ("x", _p), ("x_row_stride", _i64), ("x_rows", _i64), ("rowmap", _p), ("mel_w", _p), ("mel_b", _p),
+        ("mel", _p), ("mel_row_stride", _i64), ("mel_bf16", _p), ("w", _p * 3), ("bias", _p * 3),
+        ("B", _i), ("T", _i), ("out", _p), ("out_row_stride", _i64),
+    ]
+
+
 class CondDesc(ctypes.Structure):
     """Mirror of ``fs2_cond_desc`` (include/fs2hip.h)."""
 
@@ -494,6 +504,11 @@ SIGNATURES_PVOC = {
 }
 
 
+# include/fs2hip_postnet.h: mel_linear + the PostNet's layers 0..2 in one launch
+SIGNATURES_POSTNET = {
+    "fs2_pn_head3": (_i, [ctypes.POINTER(PnHead3Desc), _p]),
+}
+
 # include/fs2hip_iir.h: cascaded second-order sections, BS.1770 gating, the loudness gain
 SIGNATURES_IIR = {
     "fs2_iir_blocks": (_i64, [_i64]),
@@ -687,9 +702,10 @@ HEADER_F0_TRACK = os.path.join(os.path.dirname(HEADER), "fs2hip_f0_track.h")
 HEADER_VAD = os.path.join(os.path.dirname(HEADER), "fs2hip_vad.h")
 HEADER_PVOC = os.path.join(os.path.dirname(HEADER), "fs2hip_pvoc.h")
 HEADER_IIR = os.path.join(os.path.dirname(HEADER), "fs2hip_iir.h")
+HEADER_POSTNET = os.path.join(os.path.dirname(HEADER), "fs2hip_postnet.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
                  "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h",
-                 "fs2hip_pvoc.h", "fs2hip_iir.h")
+                 "fs2hip_pvoc.h", "fs2hip_iir.h", "fs2hip_postnet.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -737,7 +753,7 @@ def load():
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
             list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()) + \
-            list(SIGNATURES_PVOC.items()) + list(SIGNATURES_IIR.items()):
+            list(SIGNATURES_PVOC.items()) + list(SIGNATURES_IIR.items()) + list(SIGNATURES_POSTNET.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

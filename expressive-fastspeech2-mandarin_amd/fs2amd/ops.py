@@ -546,6 +546,45 @@ def wconv(x, w_packed, bias, *, ks, pad, out=None, second=None, layout=None, tai
     return out
 
 
+def pn_head3(x, mel_w, mel_b, convs, B, T, *, src_layout=None, mel_bf=None):
+    """mel_linear + the PostNet's first three convs in one launch (fs2_pn_head3): x the decoder's
+    bf16 rows (packed in ``src_layout``, or padded [B, T, 256]), mel_w / mel_b mel_linear's packed
+    bf16 weights [80, 256] and f32 bias, convs = ((w_packed, bias),) * 3 from
+    :func:`pack_wconv_weight`. Returns (mel f32 [B, T, 80], layer 2's output bf16 [B, T, 512]): the
+    bits of conv1d (EPI_BIAS, out2) + wconv(second=) + wconv. mel_bf: optional bf16 [B, T, 80]
+    that receives the bf16 mel (it stays on chip otherwise)."""
+    (w0, b0), (w1, b1), (w2, b2) = convs
+    _gpu(x, mel_w, mel_b, w0, b0, w1, b1, w2, b2)
+    if x.dtype != torch.bfloat16 or mel_w.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in (w0, w1, w2)):
+        raise TypeError("fs2amd.pn_head3: bf16 activations and weights only")
+    x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+    assert x2.shape[1] == 256 and mel_w.is_contiguous() and mel_w.numel() == 80 * 256 and mel_b.numel() == 80
+    assert w0.numel() == _lib.fs2_wconv_weight_elems(5, 80, 512) and b0.numel() == 512
+    assert all(w.numel() == _lib.fs2_wconv_weight_elems(5, 512, 512) and b.numel() == 512 for w, b in ((w1, b1), (w2, b2)))
+    assert all(w.is_contiguous() for w in (w0, w1, w2))
+    if src_layout is not None:
+        assert (src_layout.B, src_layout.T) == (B, T) and x2.shape[0] >= src_layout.capacity
+    else:
+        assert x2.shape[0] == B * T
+    mel = torch.empty(B, T, 80, device=x.device, dtype=torch.float32)
+    out = torch.empty(B, T, 512, device=x.device, dtype=torch.bfloat16)
+    d = L.PnHead3Desc()
+    d.x, d.x_row_stride, d.x_rows = x2.data_ptr(), _rows(x2, "x"), x2.shape[0]
+    if src_layout is not None:
+        d.rowmap = src_layout.rowmap.data_ptr()
+    d.mel_w, d.mel_b = mel_w.data_ptr(), mel_b.data_ptr()
+    d.mel, d.mel_row_stride = mel.data_ptr(), 80
+    if mel_bf is not None:
+        assert mel_bf.dtype == torch.bfloat16 and mel_bf.is_contiguous() and tuple(mel_bf.shape) == (B, T, 80)
+        d.mel_bf16 = mel_bf.data_ptr()
+    for i, (w, b) in enumerate(((w0, b0), (w1, b1), (w2, b2))):
+        d.w[i], d.bias[i] = w.data_ptr(), b.data_ptr()
+    d.B, d.T = B, T
+    d.out, d.out_row_stride = out.data_ptr(), 512
+    L.check(_lib.fs2_pn_head3(ctypes.byref(d), _stream(x)), "fs2_pn_head3")
+    return mel, out
+
+
 FFN_SLOTS = 256  # workgroups resident at once (1 per CU)
 
 

@@ -669,6 +669,9 @@ def _stage2(P, g, st, T_out, T_dec, p_control, postnet_valid=False, rows_hint=No
     if T_dec != T_out:
         dec_lens = torch.clamp(dec_lens, max=T_dec)
     x = _stack(P, P.dec_layers, x, dec_lens, timed=True)
+    if pn_head3_ok(P, x, postnet_valid):
+        mel, y = _pn_head3(P, x, x.shape[0], x.shape[1])
+        return mel, _postnet_convs(P, y, mel, first=3), st
     mel_bf = _mel_copy(P, x, x.shape[:2])
     mel = ops.conv1d(x, P.mel_w, P.mel_b, cin=P.d_model, ks=1, pad=0, compute=P.compute, epilogue=L.EPI_BIAS,
                      out_dtype=L.FS2_F32, out2=mel_bf)
@@ -753,6 +756,10 @@ def mel_postnet(P, x, lay, dec_lens, postnet_valid=False, rows_hint=None):
     """mel_linear from the packed decoder rows into the padded [B, lay.T, n_mel] contract (padded
     frames get the bias, as the reference's masked decoder output gives) and the PostNet +
     residual with the reference's padded semantics over lay.T frames."""
+    if pn_head3_ok(P, x, postnet_valid):
+        with _Timed("dec:postnet"):
+            mel, y = _pn_head3(P, x, lay.B, lay.T, lay)
+            return mel, _postnet_convs(P, y, mel, first=3)
     mel_bf = _mel_copy(P, x, (lay.B, lay.T))
     with _Timed("dec:mel"):
         mel = ops.conv1d(x, P.mel_w, P.mel_b, cin=P.d_model, ks=1, pad=0, compute=P.compute, epilogue=L.EPI_BIAS,
@@ -952,6 +959,26 @@ def pn_head_on():
     return os.environ.get("FS2_PN_HEAD", "1") != "0"
 
 
+def pn_head3_on():
+    """FS2_PN_HEAD3=0: mel_linear, the PostNet's layers 0 + 1 and layer 2 as three launches (A/B)."""
+    return os.environ.get("FS2_PN_HEAD3", "1") != "0"
+
+
+def pn_head3_ok(P, x, postnet_valid=False):
+    """mel_linear and the PostNet's layers 0..2 go in one launch (fs2_pn_head3): wherever layers
+    0 + 1 take their one launch today with bf16 activations, on padded rows. The valid-region
+    PostNet (packed rows: free-running batches padded to one long utterance) keeps its launches."""
+    pn = P.postnet
+    return (pn_head3_on() and pn_head_on() and wconv_on() and not postnet_valid and _mel_copy_on(P)
+            and x.dtype == torch.bfloat16 and x.shape[-1] == 256 and P.mel_w.numel() == 80 * 256 and len(pn) > 3
+            and all(getattr(l, "wfr", None) is not None and l.k == 5 and l.p == 2 for l in pn[:3])
+            and pn[0].cin == 80 and pn[1].cin == 512 and pn[2].cin == 512)
+
+
+def _pn_head3(P, x, B, T, lay=None):
+    return ops.pn_head3(x, P.mel_w, P.mel_b, [(l.wfr, l.b) for l in P.postnet[:3]], B, T, src_layout=lay)
+
+
 def pn_tail_fused_on():
     """FS2_PN_TAIL_FUSED=0: the PostNet's last conv + residual as its own fs2_wconv launch (A/B)."""
     return os.environ.get("FS2_PN_TAIL_FUSED", "1") != "0"
@@ -995,14 +1022,14 @@ def _postnet(P, mel, mel_bf=None, mel_len=None, sum_len=None):
     return _postnet_convs(P, y, mel)
 
 
-def _postnet_convs(P, y, res, layout=None):
+def _postnet_convs(P, y, res, layout=None, first=0):
     """The PostNet's convs (BN folded) on y (mel's bf16 copy, or the f32 mel) + the residual res
     (f32 mel); padded [B, T, C] rows, or packed rows of ``layout`` (the valid-region form). Both
     forms take the same kernels: fs2_wconv for layers 0 + 1 (one launch), 2, 3 and the last conv +
-    residual (its N = 80 form); fs2_conv1d where those shapes do not apply."""
+    residual (its N = 80 form); fs2_conv1d where those shapes do not apply. first: y is already
+    the output of layer first - 1 (fs2_pn_head3 ran mel_linear and layers 0..2)."""
     n_pn = len(P.postnet)
-    first = 0
-    if n_pn > 2 and y.dtype == torch.bfloat16 and wconv_on() and pn_head_on() and \
+    if first == 0 and n_pn > 2 and y.dtype == torch.bfloat16 and wconv_on() and pn_head_on() and \
             getattr(P.postnet[0], "wfr", None) is not None and getattr(P.postnet[1], "wfr", None) is not None and \
             P.postnet[0].cin == 80 and P.postnet[0].k == 5 and P.postnet[0].p == 2 and P.postnet[1].p == 2:
         # layers 0 and 1 (80 -> 512 -> 512) in one launch: the first conv's output stays on chip
