@@ -955,7 +955,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         bool masked = false;
         int bb = 0;
         if constexpr (padded) {
-          bb = (m0 + m) / T;
+          // rows past M (the last tile) are computed and not stored: their utterance is clamped as
+          // their lens entry is above, or the addvec loads below read past the [B, D] vectors
+          bb = min(m0 + m, M - 1) / T;
           masked = (padmask >> mb) & 1;
         }
 #pragma unroll

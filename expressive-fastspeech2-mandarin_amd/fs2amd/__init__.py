@@ -7,6 +7,7 @@ from .align import AlignmentEncoder, ForwardSumLoss, fit_aligner, mas_durations
 from .augment import augment_utterances, pitch_shift, time_stretch
 from .audio import (STFT, TacotronSTFT, extract_features, get_mel_from_wav, griffin_lim, inv_mel_spec, mel_filterbank,
                     mel_to_wav, window_sumsquare)
+from .emotion import curve, level_weights, mixture, one_hot
 from .evaluate import dtw, evaluate, f0_metrics, mcd, mel_cepstrum
 from .loss import FastSpeech2Loss
 from .loudness import integrated_loudness, normalize_loudness
@@ -20,5 +21,6 @@ __all__ = ["FastSpeech2", "FastSpeech2Loss", "ScheduledOptim", "LengthRegulator"
            "mel_to_wav", "window_sumsquare", "get_alignment", "pitch_targets", "remove_outlier", "CorpusStats",
            "normalize", "build_corpus", "f0_contour", "prepare_wavs", "ForwardSumLoss", "AlignmentEncoder",
            "mas_durations", "fit_aligner", "trim_silence", "split_silence", "time_stretch", "pitch_shift",
-           "augment_utterances", "integrated_loudness", "normalize_loudness", "mcd", "dtw", "mel_cepstrum",
+           "augment_utterances", "integrated_loudness", "normalize_loudness", "mixture", "level_weights",
+           "curve", "one_hot", "mcd", "dtw", "mel_cepstrum",
            "f0_metrics", "evaluate"]

@@ -156,6 +156,18 @@ class CondDesc(ctypes.Structure):
     ]
 
 
+class CondMixDesc(ctypes.Structure):
+    """Mirror of ``fs2_cond_mix_desc`` (include/fs2hip_cond_mix.h)."""
+
+    _fields_ = [
+        ("speakers", _p), ("spk_kind", _i), ("speaker_table", _p), ("n_speaker", _i),
+        ("emotions", _p), ("emo_kind", _i), ("emo_table", _p), ("n_emo", _i), ("d_emo", _i),
+        ("arousals", _p), ("aro_kind", _i), ("aro_table", _p), ("n_aro", _i), ("d_aro", _i),
+        ("valences", _p), ("val_kind", _i), ("val_table", _p), ("n_val", _i), ("d_val", _i),
+        ("lin_w", _p), ("lin_b", _p), ("B", _i), ("D", _i), ("spk_out", _p), ("emo_out", _p),
+    ]
+
+
 class CondGrads(ctypes.Structure):
     """Mirror of ``fs2_cond_grads`` (include/fs2hip.h)."""
 
@@ -521,6 +533,14 @@ SIGNATURES_IIR = {
 }
 
 
+# include/fs2hip_cond_mix.h: conditioning vectors from weights over the embedding rows
+COND_NONE, COND_IDS, COND_MIX, COND_ROWS = 0, 1, 2, 3  # FS2_COND_NONE / _IDS / _MIX / _ROWS
+SIGNATURES_COND_MIX = {
+    "fs2_cond_mix": (_i, [ctypes.POINTER(CondMixDesc), _p]),
+    "fs2_cond_mix_rows": (_i, [ctypes.POINTER(CondMixDesc), _i, _p, _i, _p]),
+}
+
+
 def iir_blocks(n):
     """iir_blocks of csrc/iir_sizes.h: 0 for n < 1, else ceil(n / 64)."""
     return 0 if n < 1 else (n - 1) // IIR_BLOCK + 1
@@ -703,9 +723,10 @@ HEADER_VAD = os.path.join(os.path.dirname(HEADER), "fs2hip_vad.h")
 HEADER_PVOC = os.path.join(os.path.dirname(HEADER), "fs2hip_pvoc.h")
 HEADER_IIR = os.path.join(os.path.dirname(HEADER), "fs2hip_iir.h")
 HEADER_POSTNET = os.path.join(os.path.dirname(HEADER), "fs2hip_postnet.h")
+HEADER_COND_MIX = os.path.join(os.path.dirname(HEADER), "fs2hip_cond_mix.h")
 EXTRA_HEADERS = ("fs2hip_prosody.h", "fs2hip_audio.h", "fs2hip_audio_inv.h", "fs2hip_prep.h", "fs2hip_f0.h",
                  "fs2hip_resample.h", "fs2hip_align.h", "fs2hip_eval.h", "fs2hip_f0_track.h", "fs2hip_vad.h",
-                 "fs2hip_pvoc.h", "fs2hip_iir.h", "fs2hip_postnet.h")
+                 "fs2hip_pvoc.h", "fs2hip_iir.h", "fs2hip_postnet.h", "fs2hip_cond_mix.h")
 
 
 def source_build_id(csrc=CSRC, header=HEADER):
@@ -753,7 +774,8 @@ def load():
             list(SIGNATURES_AUDIO.items()) + list(SIGNATURES_AUDIO_INV.items()) + list(SIGNATURES_PREP.items()) + \
             list(SIGNATURES_F0.items()) + list(SIGNATURES_RESAMPLE.items()) + list(SIGNATURES_ALIGN.items()) + \
             list(SIGNATURES_EVAL.items()) + list(SIGNATURES_F0_TRACK.items()) + list(SIGNATURES_VAD.items()) + \
-            list(SIGNATURES_PVOC.items()) + list(SIGNATURES_IIR.items()) + list(SIGNATURES_POSTNET.items()):
+            list(SIGNATURES_PVOC.items()) + list(SIGNATURES_IIR.items()) + list(SIGNATURES_POSTNET.items()) + \
+            list(SIGNATURES_COND_MIX.items()):
         if allow_missing and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -128,18 +128,20 @@ class SynthGraphs:
         self._g2.clear()
 
     @staticmethod
-    def _inputs(dev, speakers, emotions, arousals, valences, texts, src_lens, p_targets, e_targets):
+    def _inputs(dev, cond, texts, src_lens, p_targets, e_targets):
+        """cond: the four conditioning inputs from runtime.cond_inputs (int64 ids, or f32 weights,
+        which are graph inputs like the control maps)."""
         i64 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.int64).contiguous()
         f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-        return dict(speakers=i64(speakers), emotions=i64(emotions), arousals=i64(arousals), valences=i64(valences),
-                    texts=i64(texts), src_lens=i64(src_lens), p_targets=f32(p_targets), e_targets=f32(e_targets))
+        return dict(**cond, texts=i64(texts), src_lens=i64(src_lens), p_targets=f32(p_targets),
+                    e_targets=f32(e_targets))
 
-    def _stage1_body(self, P, va, s, Lx, controls):
+    def _stage1_body(self, P, va, s, Lx, controls, cond_forms=R.ALL_IDS):
         p_c, e_c, d_c = controls  # numbers, or the static [B, L] control-map buffers
         g = SimpleNamespace(speakers=s["speakers"], emotions=s["emotions"], arousals=s["arousals"],
-                            valences=s["valences"], texts=s["texts"], lens_src=s["src_lens"], Lx=Lx,
-                            p_targets=s["p_targets"], e_targets=s["e_targets"], d_targets=None, mel_lens=None,
-                            mask_out=None)
+                            valences=s["valences"], cond_forms=cond_forms, texts=s["texts"], lens_src=s["src_lens"],
+                            Lx=Lx, p_targets=s["p_targets"], e_targets=s["e_targets"], d_targets=None,
+                            mel_lens=None, mask_out=None)
         src_masks = None
         if R.embed_block_ok(P, Lx):
             # the first encoder block's launch builds its input and writes the source mask
@@ -183,9 +185,14 @@ class SynthGraphs:
         # numbers stay numbers (and keep their value in the key); maps become f32 [B, Lx] tensors
         p_c, e_c, d_c = R.prosody_controls(va, p_control, e_control, d_control, B, Lx, dev)
         kc = lambda c: "map" if torch.is_tensor(c) else float(c)
-        x = self._inputs(dev, speakers, emotions, arousals, valences, texts, src_lens, p_targets, e_targets)
+        # ids, or weights over the embedding rows: one marker each in the key ("ids", ("mix", n),
+        # ("curve", n)); the weights are graph inputs, so one graph per shape serves every value
+        cond, cond_forms = R.cond_inputs(P, speakers, emotions, arousals, valences, B, Lx, dev)
+        x = self._inputs(dev, cond, texts, src_lens, p_targets, e_targets)
         key1 = (model._precision, model._vp_precision, B, Lx, (kc(p_control), kc(e_control), kc(d_control)),
                 tuple(k for k, v in x.items() if v is None))
+        if cond_forms != R.ALL_IDS:
+            key1 += (cond_forms,)
         if getattr(va, "separate_energy_control", False):
             key1 += ("separate_energy",)
         # mapped controls are graph inputs like the batch: a static buffer each, filled by the copy below
@@ -204,7 +211,8 @@ class SynthGraphs:
             static = {k: (None if v is None else v.clone()) for k, v in x.items()}
             sp, sd = static.get("p_control", p_c), static.get("d_control", d_c)
             controls = (sp, sp if e_c is p_c else static.get("e_control", e_c), sd)
-            graph, (g, st, src_masks, meta) = self._capture(lambda: self._stage1_body(P, va, static, Lx, controls))
+            graph, (g, st, src_masks, meta) = self._capture(
+                lambda: self._stage1_body(P, va, static, Lx, controls, cond_forms))
             meta_host = torch.empty(meta.shape, dtype=meta.dtype, pin_memory=True)
             e1 = self._g1[key1] = SimpleNamespace(graph=graph, static=static, g=g, st=st, src_masks=src_masks,
                                                   meta=meta, meta_host=meta_host, meta_np=meta_host.numpy(), P=P,

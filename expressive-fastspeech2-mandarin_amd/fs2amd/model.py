@@ -280,6 +280,12 @@ class FastSpeech2(nn.Module):
                 max_mel_len=None, p_targets=None, e_targets=None, d_targets=None, p_control=1.0, e_control=1.0,
                 d_control=1.0):
         if self.training:
+            # mixtures / curves (floating conditioning inputs, runtime.cond_inputs) are synthesis controls
+            for name, t in (("speakers", speakers), ("emotions", emotions), ("arousals", arousals),
+                            ("valences", valences)):
+                if torch.is_tensor(t) and t.is_floating_point():
+                    raise ValueError(f"fs2amd: {name} is a floating tensor (mixture weights): training takes ids; "
+                                     f"call model.eval() for synthesis")
             # train.py step: dropout, batch-statistic BatchNorm, autograd (fs2amd/training.py)
             from .training import train_forward
 

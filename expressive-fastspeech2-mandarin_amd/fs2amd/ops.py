@@ -1033,6 +1033,82 @@ def cond_vectors(speakers, spk_table, emotions, arousals, valences, emo_table, a
     return spk_out, emo_out
 
 
+def _cond_kind(t, n, B, rows, name):
+    """The FS2_COND_* kind of one conditioning input: int64 ids [B], f32 weights [B, n] or (rows
+    = B * L given) f32 weights [B, L, n] / [B * L, n]."""
+    if t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == B:
+        return L.COND_IDS
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != n:
+        raise ValueError(f"fs2amd: {name} must be int64 [B] or contiguous float32 weights [.., {n}], got "
+                         f"{t.dtype} {tuple(t.shape)}")
+    if t.dim() == 2 and t.shape[0] == B:
+        return L.COND_MIX
+    if rows is not None and t.numel() == rows * n and (t.dim() == 3 and t.shape[0] == B or t.dim() == 2):
+        return L.COND_ROWS
+    raise ValueError(f"fs2amd: {name} weights of shape {tuple(t.shape)} for B = {B}" +
+                     ("" if rows is None else f", B * L = {rows}"))
+
+
+def _cond_mix_desc(speakers, spk_table, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w, lin_b,
+                   B, D, rows=None):
+    cd = L.CondMixDesc()
+    cd.B, cd.D = B, D
+    if spk_table is not None:
+        cd.speakers, cd.speaker_table, cd.n_speaker = _ptr(speakers), _ptr(spk_table), spk_table.shape[0]
+        cd.spk_kind = _cond_kind(speakers, spk_table.shape[0], B, None, "speakers")
+    if emo_table is not None:
+        for nm, t, tab in (("emo", emotions, emo_table), ("aro", arousals, aro_table), ("val", valences, val_table)):
+            setattr(cd, {"emo": "emotions", "aro": "arousals", "val": "valences"}[nm], _ptr(t))
+            setattr(cd, nm + "_kind", _cond_kind(t, tab.shape[0], B, rows, nm))
+            setattr(cd, nm + "_table", _ptr(tab))
+            setattr(cd, "n_" + nm, tab.shape[0])
+            setattr(cd, "d_" + nm, tab.shape[1])
+        cd.lin_w, cd.lin_b = _ptr(lin_w), _ptr(lin_b)
+    return cd
+
+
+def cond_mix(speakers, spk_table, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w, lin_b, D,
+             spk_out=None, emo_out=None):
+    """fs2_cond_mix (include/fs2hip_cond_mix.h): :func:`cond_vectors` where each of speakers /
+    emotions / arousals / valences is int64 ids [B] or contiguous f32 weights [B, n] over its
+    table's rows (used as given: not normalised). One launch; the bits of cond_vectors for ids and
+    for one-hot rows. Returns (spk_out, emo_out) f32 [B, D] (None without the table; written into
+    the contiguous f32 [B, D] tensors given as spk_out / emo_out, else new)."""
+    ref = speakers if speakers is not None else emotions
+    _gpu(ref, speakers, emotions, arousals, valences, spk_out, emo_out)
+    B = ref.shape[0]
+    for o in (spk_out, emo_out):
+        if o is not None and (o.dtype != torch.float32 or tuple(o.shape) != (B, D) or not o.is_contiguous()):
+            raise ValueError(f"fs2amd: cond_mix outputs must be contiguous float32 [{B}, {D}]")
+    if spk_table is None:
+        spk_out = None
+    elif spk_out is None:
+        spk_out = torch.empty(B, D, device=ref.device)
+    if emo_table is None:
+        emo_out = None
+    elif emo_out is None:
+        emo_out = torch.empty(B, D, device=ref.device)
+    cd = _cond_mix_desc(speakers, spk_table, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w,
+                        lin_b, B, D)
+    cd.spk_out, cd.emo_out = _ptr(spk_out), _ptr(emo_out)
+    L.check(_lib.fs2_cond_mix(ctypes.byref(cd), _stream(ref)), "fs2_cond_mix")
+    return spk_out, emo_out
+
+
+def cond_mix_rows(x, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w, lin_b):
+    """fs2_cond_mix_rows: x [B, L, D] (f32 or bf16, contiguous) += the emotion vector of every
+    position, IN PLACE, one launch. Each of emotions / arousals / valences is int64 ids [B], f32
+    weights [B, n] (both broadcast over L) or f32 weights [B, L, n]. Returns x."""
+    _gpu(x, emotions, arousals, valences)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("fs2amd: cond_mix_rows needs a contiguous [B, L, D] tensor")
+    B, Lx, D = x.shape
+    cd = _cond_mix_desc(None, None, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w, lin_b, B, D,
+                        rows=B * Lx)
+    L.check(_lib.fs2_cond_mix_rows(ctypes.byref(cd), Lx, _ptr(x), _dt(x), _stream(x)), "fs2_cond_mix_rows")
+    return x
+
+
 def cond_bwd(dy, speakers, spk_table, emotions, arousals, valences, emo_table, aro_table, val_table, lin_w, emo_out,
              d_spk=None, d_emo=None, d_aro=None, d_val=None, d_w=None, d_b=None):
     """Backward of y = x + spk_out[b] + emo_out[b] (fs2_cond_bwd): ACCUMULATES the speaker /

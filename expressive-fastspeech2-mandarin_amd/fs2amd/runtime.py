@@ -520,6 +520,52 @@ class _ForkJoin:
                     t.record_stream(self.main)
 
 
+COND_NAMES = ("speakers", "emotions", "arousals", "valences")
+ALL_IDS = ("ids",) * 4
+
+
+def cond_inputs(P, speakers, emotions, arousals, valences, B, Lx, dev):
+    """The four conditioning inputs as the kernels take them, and the form of each.
+
+    An input is ids (anything that is not a floating tensor: cast to int64 [B] on ``dev``, as
+    always), an utterance mixture (floating [B, n], n = the rows of its embedding table) or, for
+    emotions / arousals / valences, a per-phoneme curve (floating [B, Lx, n]). Weights become
+    contiguous f32; they are used as given (not normalised) and must be finite, which is the
+    caller's duty (no check: it would cost a host sync). ValueError: a floating tensor that is not
+    on ``dev``, has another rank, the wrong n or Lx, or a curve for speakers. Returns
+    ({name: tensor or None}, forms) with forms[i] "ids", ("mix", n) or ("curve", n) in the order
+    of COND_NAMES; an input whose table the model lacks is never read and counts as ids."""
+    tables = (P.spk_table, P.emo_table, getattr(P, "aro_table", None) if P.emo_table is not None else None,
+              getattr(P, "val_table", None) if P.emo_table is not None else None)
+    dev = torch.device(dev)
+    out, forms = {}, []
+    for name, t, table in zip(COND_NAMES, (speakers, emotions, arousals, valences), tables):
+        if not (torch.is_tensor(t) and t.is_floating_point()):
+            out[name] = None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.int64).contiguous()
+            forms.append("ids")
+            continue
+        if t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+            raise ValueError(f"fs2amd: {name} weights are on {t.device} but the model runs on {dev}")
+        if t.dim() == 3 and name == "speakers":
+            raise ValueError("fs2amd: speakers takes ids [B] or a mixture [B, n]; per-phoneme curves are for "
+                             "emotions / arousals / valences")
+        if t.dim() not in (2, 3):
+            raise ValueError(f"fs2amd: {name} weights must be [B, n] or [B, max_src_len, n], got {tuple(t.shape)} "
+                             f"(ids are an integer tensor)")
+        if table is None:  # the model has no such table: not read
+            out[name] = None
+            forms.append("ids")
+            continue
+        n = table.shape[0]
+        want = (B, n) if t.dim() == 2 else (B, Lx, n)
+        if tuple(t.shape) != want:
+            raise ValueError(f"fs2amd: {name} weights of shape {tuple(t.shape)}, expected {want} "
+                             f"([B{'' if t.dim() == 2 else ', max_src_len'}, rows of the table])")
+        out[name] = t.detach().to(torch.float32).contiguous()
+        forms.append(("mix" if t.dim() == 2 else "curve", n))
+    return out, tuple(forms)
+
+
 def _stage1(P, va, g, p_control, d_control, defer_lr=False, e_control=None):
     """Encoder (+ conditioning), variance predictors, duration scan for one utterance group.
     defer_lr (teacher-forced durations, decoder length known): the duration scan is left to the
@@ -535,7 +581,20 @@ def _stage1(P, va, g, p_control, d_control, defer_lr=False, e_control=None):
     # FS2_ENC_COND=1: the conditioning tiles on extra workgroups of the first block's launch (A/B:
     # 32.4 us for that launch against 16.8 + 9.2 for the block and fs2_cond_vectors, profiles/r5ck)
     cond_fold = fold and os.environ.get("FS2_ENC_COND", "0") == "1"
-    if has_cond and not cond_fold:
+    # weights in place of ids (cond_inputs): fs2_cond_mix; with a per-phoneme curve the emotion part
+    # is added by fs2_cond_mix_rows after the stack and only the speaker vector rides the epilogue
+    forms = getattr(g, "cond_forms", ALL_IDS)
+    curve = has_cond and any(f != "ids" and f[0] == "curve" for f in forms)
+    if has_cond and forms != ALL_IDS:
+        cond_fold = False
+        emo = None if curve else P.emo_table
+        if P.spk_table is not None or emo is not None:
+            spk_vec, emo_vec = ops.cond_mix(
+                g.speakers if P.spk_table is not None else None, P.spk_table,
+                g.emotions if emo is not None else None, g.arousals, g.valences, emo,
+                getattr(P, "aro_table", None), getattr(P, "val_table", None), getattr(P, "emo_w", None),
+                getattr(P, "emo_b", None), P.d_model)
+    elif has_cond and not cond_fold:
         spk_vec, emo_vec = ops.cond_vectors(
             g.speakers if P.spk_table is not None else None, P.spk_table,
             g.emotions if P.emo_table is not None else None, g.arousals, g.valences, P.emo_table,
@@ -574,6 +633,9 @@ def _stage1(P, va, g, p_control, d_control, defer_lr=False, e_control=None):
         x = _stack(P, P.enc_layers, x, g.lens_src, addvecs=(spk_vec, emo_vec))
     if n_enc == 0 and (spk_vec is not None or emo_vec is not None):
         raise NotImplementedError("encoder_layer = 0")
+    if curve:
+        x = ops.cond_mix_rows(x, g.emotions, g.arousals, g.valences, P.emo_table, P.aro_table, P.val_table, P.emo_w,
+                              P.emo_b)
 
     st = SimpleNamespace(x=x, p_pred=None, e_pred=None)
     st.phoneme_p = va.pitch_feature_level == "phoneme_level"
@@ -801,8 +863,9 @@ def run_forward(model, speakers, emotions, arousals, valences, texts, src_lens, 
     else:
         src_masks = _mask(src_lens, Lx)
         mel_masks = _mask(mel_lens, mel_w) if mel_lens is not None else None
+    cond, cond_forms = cond_inputs(P, speakers, emotions, arousals, valences, B, Lx, dev)
     full = SimpleNamespace(
-        speakers=ids(speakers), emotions=ids(emotions), arousals=ids(arousals), valences=ids(valences),
+        **cond, cond_forms=cond_forms,
         texts=ids(texts), lens_src=src_lens.to(torch.int64).contiguous(), Lx=Lx,
         p_targets=f32(p_targets), e_targets=f32(e_targets),
         d_targets=None if d_targets is None else d_targets.to(dev),
